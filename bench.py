@@ -6,7 +6,12 @@ Workload (BASELINE.json configs[1], "B"): a synthetic 1 GiB bitcaskDB WAL segmen
 (bcw_synth_segment) and copied to HBM before timing. One "step" = one full decode of the
 segment through the C-ABI (bcw_decode_segment_async): header chase, CRC-32C verify of every
 fragment, record assembly and RecordFromBytes for every record into the device record table.
-An extra `pipelined` key times the same K steps rotating over --inflight (default 2) independent
+A plain run does what the headline needs and no more: it builds and checks the segment's decode once,
+runs the W untimed and K timed steps, writes the last step's record table with --dump-outputs DIR, and
+prints the result line. --full adds every other leg after the timed steps: the per-kernel times, the
+PCIe-inclusive rate, config C, the config-E encode, the file-to-file rates and the CPU baselines
+(--no-cpu-baseline, --no-extras and --encode-records 0 drop some of them again), and the
+`pipelined` key, which times the same K steps rotating over --inflight (default 2) independent
 segments, each with its own context (stream, scratch, record table), as a scan over many WAL files
 runs: one segment's latency-bound kernels overlap the next one's CRC pass.
 Multi-GPU = config D: every rank decodes its own independent segment (seed 42 + rank) with no
@@ -44,15 +49,23 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--seg-bytes", type=int, default=1 << 30)
     ap.add_argument("--config", default="B", choices=["B", "C"], help="B: 4 KiB values; C: Zipf 128 B-64 KiB")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (per-kernel times, pipelined, PCIe-inclusive, "
+                         "config C, config-E encode, file-to-file rates, CPU baselines); a plain run times the headline "
+                         "alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step decoded (the record table's columns over the decoded records "
+                         "and the decode result) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="bounded CPU-baseline sample (rank 0, N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra legs (config C, all-core / pread CPU baselines, file-to-file end-to-end rates)")
+                    help="with --full: skip the extra legs (config C, all-core / pread CPU baselines, file-to-file "
+                         "end-to-end rates)")
     ap.add_argument("--encode-records", type=int, default=10_000_000,
                     help="records of the extra encode_e leg (BASELINE.json configs[4], config E: 10 M); 0 skips it")
     ap.add_argument("--cpu-threads", type=int, default=16, help="threads of the all-core CPU baseline")
     ap.add_argument("--inflight", type=int, default=2,
-                    help="segments in flight for the extra pipelined leg: steps rotate over this many contexts "
+                    help="segments in flight for the extra pipelined leg (--full): steps rotate over this many contexts "
                          "(own stream, segment, record table); the headline value is one segment at a time")
     ap.add_argument("--event-every", type=int, default=4,
                     help="HIP events bracket every N-th k_crc launch of the timed region")
@@ -62,6 +75,38 @@ def parse():
                          "report as roofline.traffic; used only when its decode_src_sha16 matches this build's "
                          "decode sources (bitcaskdb_amd/build.py decode_src_sha16)")
     return ap.parse_args()
+
+
+DUMP_BUDGET = 64 << 20  # bytes of .npy payload per --dump-outputs directory
+RESULT_FIELDS = ("n_records", "n_records_total", "n_frags", "err_frag", "err_file_off", "err_class",
+                 "first_bad_record", "n_blocks", "retry_frag_capacity")  # not `generation`: a per-context call counter
+
+
+def dump_outputs(path, L, cols, d_res, prefix=""):
+    """--dump-outputs: what a caller of the timed decode receives, as it stands after the last timed step: the decode
+    result (RESULT_FIELDS, float64) and every record-table column over the n_records decoded rows (u64 / u32 columns
+    as float64, u8 columns as float32; rows past n_records are never written by the decode). Above DUMP_BUDGET the
+    same seeded sample of rows is kept from every column and its row numbers are written as sample_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    res = L.DecodeResult.from_buffer_copy(bytes(d_res.cpu().numpy()))
+    np.save(os.path.join(path, prefix + "result.npy"),
+            np.array([float(getattr(res, f)) for f in RESULT_FIELDS], dtype=np.float64))
+    n = int(res.n_records)
+    out_dt = {name: (np.float32 if dt == "u1" else np.float64) for name, dt in L.TABLE_COLUMNS if name in cols}
+    row_bytes = sum(np.dtype(d).itemsize for d in out_dt.values())
+    rows = None
+    if n * row_bytes > DUMP_BUDGET:
+        keep = DUMP_BUDGET // (row_bytes + 8)  # + the row number itself
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        np.save(os.path.join(path, prefix + "sample_rows.npy"), rows.astype(np.float64))
+    view = {"u8": np.uint64, "u4": np.uint32, "u1": np.uint8}
+    for name, dt in L.TABLE_COLUMNS:
+        if name not in cols:
+            continue
+        a = cols[name][:n].cpu().numpy().view(view[dt])
+        if rows is not None:
+            a = a[rows]
+        np.save(os.path.join(path, prefix + name + ".npy"), a.astype(out_dt[name]))
 
 
 def cpu_model() -> str:
@@ -348,7 +393,7 @@ def main():
     # kernel boundaries overlap another segment's CRC pass. Every step is still one complete decode of one
     # whole segment; the steps rotate over the contexts.
     vmode = 0 if args.config == "B" else 1
-    nslot = max(1, args.inflight)
+    nslot = max(1, args.inflight) if args.full else 1  # a plain run needs the headline's one segment only
 
     def build_segment(seed):
         n, r = C.c_uint64(), C.c_uint64()
@@ -465,12 +510,15 @@ def main():
     ev_ms = ev0.elapsed_time(ev1)
     crc_ms, crc_samples = kernel_times(all_ctx)[roof_name]
     bytes_total = seg_len * args.steps
+    for cx in all_ctx:
+        L.lib.bcw_ctx_set_profiling(cx.handle, 0)
+    # the record table and result as the last timed step left them, before any other leg decodes into them again
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, L, s0["cols"], d_res, "" if rank == 0 else f"rank{rank}_")
     # pipelined: the same K steps rotating over the in-flight segments (an extra key, never `value`: with two
     # streams a k_crc event pair also spans the other segment's kernels)
     pipelined = None
     if nslot > 1:
-        for cx in all_ctx:
-            L.lib.bcw_ctx_set_profiling(cx.handle, 0)
         wall_p = shard.timed_steps(step_rot, args.steps, 0, torch.cuda.synchronize,
                                    dist.barrier if world > 1 else None)
         wall_p = shard.max_over_ranks(wall_p, dist, red_dev)
@@ -481,13 +529,15 @@ def main():
                      "note": "steps rotate over independent segments on their own contexts/streams (a multi-file "
                              "scan): one segment's k_chase and the kernel boundaries overlap the next one's k_crc"}
     # every kernel's average, one segment at a time (untimed repeat, events around each kernel)
-    L.lib.bcw_ctx_set_profiling_sample(ctx.handle, 1)
-    L.lib.bcw_ctx_set_profiling(ctx.handle, -1)
-    for _ in range(min(args.steps, 10)):
-        step()
-    kern = {k: v[0] for k, v in kernel_times([ctx]).items()}
-    for cx in all_ctx:
-        L.lib.bcw_ctx_set_profiling(cx.handle, 0)
+    kern = None
+    if args.full:
+        L.lib.bcw_ctx_set_profiling_sample(ctx.handle, 1)
+        L.lib.bcw_ctx_set_profiling(ctx.handle, -1)
+        for _ in range(min(args.steps, 10)):
+            step()
+        kern = {k: v[0] for k, v in kernel_times([ctx]).items()}
+        for cx in all_ctx:
+            L.lib.bcw_ctx_set_profiling(cx.handle, 0)
 
     wall_max = shard.max_over_ranks(wall, dist, red_dev)
     ms_per_step = wall_max / args.steps * 1e3
@@ -496,7 +546,7 @@ def main():
 
     # end-to-end PCIe-inclusive rate (pinned H2D of the segment + decode), rank 0 only, not `value`
     pcie = None
-    if rank == 0:
+    if args.full and rank == 0:
         torch.cuda.synchronize()
         t = time.perf_counter()
         reps = 3
@@ -535,20 +585,21 @@ def main():
                 "kernel": roof_name,
                 "kernel_ms": round(crc_ms, 4), "kernel_launches_timed": crc_samples, "alg_bytes": alg_bytes,
                 "pipeline_GBs": round(bytes_total / args.steps / (ms_per_step * 1e-3) / 1e9, 1),
-                "kernel_ms_all": {k: round(v, 4) for k, v in kern.items()}}
+                "kernel_ms_all": {k: round(v, 4) for k, v in kern.items()} if kern is not None else None}
 
-    # ---- config C and end-to-end through the host I/O staging (rank 0, N=1) ----
+    # ---- config C and end-to-end through the host I/O staging (--full, rank 0, N=1) ----
     extras = {}
-    if world == 1 and not args.no_extras and args.config == "B":
+    with_extras = args.full and world == 1 and not args.no_extras
+    if with_extras and args.config == "B":
         extras["config_c"] = config_c_leg(L, Context, torch, dev, args, make_table, roof_name, names)
-    if world == 1 and not args.no_extras and args.config == "B" and args.encode_records > 0:
+    if with_extras and args.config == "B" and args.encode_records > 0:
         extras["encode_e"] = encode_e_leg(args)
-    if world == 1 and not args.no_extras:
+    if with_extras:
         extras["e2e"] = end_to_end(L, ctx, stream, host, d_seg, step, table, d_res, seg_len, n_rec)
 
-    # ---- CPU baseline: restated reference decode loop (oracle/, hardware CRC, 1 thread) ----
+    # ---- CPU baseline (--full): restated reference decode loop (oracle/, hardware CRC, 1 thread) ----
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import _oracle as O  # noqa: E402  (cpu_baseline leg only)
         hb = host.numpy()
@@ -579,7 +630,7 @@ def main():
     line = {
         "metric": METRIC, "value": round(value, 2), "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "vs_baseline": None, "dtype": "u8", "data": "synthetic", "full": args.full,
         "config": {"workload": f"config {args.config}: {seg_len} B WAL segment per GPU, NsSize 20, 100 B keys, "
                                + ("4 KiB values" if args.config == "B" else "Zipf(1.1) 128 B-64 KiB values")
                                + ", device-resident decode+CRC+record parse",

@@ -22,7 +22,7 @@ if has smoke; then
 fi
 if has bench; then
   run bench
-  timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1 || { tail -30 "$OUT/bench.log"; exit 1; }
+  timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1 || { tail -30 "$OUT/bench.log"; exit 1; }
   tail -1 "$OUT/bench.log"
 fi
 if has kbench; then

@@ -2,7 +2,7 @@
 # Round-6 GPU runs (one gpurun call): STEPS picks from
 #   tests   the -m gpu suite (TESTS selects files, default the whole suite; PYK a -k expression)
 #   smoke   __graft_entry__.smoke()
-#   bench   bench.py exactly as the driver runs it (config B, --warmup 5 --steps 20)
+#   bench   bench.py --full with the driver's steps (config B, --warmup 5 --steps 20): the headline and every extra leg
 #   kb      tools/kbench default mode on config B and C (pipeline and per-kernel times, k_chase phase stamps)
 #   cmp     tools/kbench k_crc variants (VARIANTS) interleaved, config B and C, in-kernel clock
 #   xbal    tools/kbench pipelines with the per-XCD split on / off (config B and C)
@@ -33,7 +33,7 @@ if has smoke; then
 fi
 if has bench; then
   echo "== bench $(date +%T)"
-  timeout -k 10 500 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.log" 2>&1 || { tail -30 "$OUT/bench.log"; exit 1; }
+  timeout -k 10 500 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench.log" 2>&1 || { tail -30 "$OUT/bench.log"; exit 1; }
   tail -1 "$OUT/bench.log" > "$OUT/bench.json"; cut -c1-600 "$OUT/bench.json"
 fi
 if has kb; then
