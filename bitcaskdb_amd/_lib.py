@@ -177,6 +177,7 @@ def _load():
         "bcw_index_reserve": (C.c_int, [vp, C.c_uint64, C.c_uint64]),
         "bcw_index_stats": (C.c_int, [vp, C.POINTER(IndexInfo)]),
         "bcw_index_set_limit": (C.c_int, [vp, C.c_uint64]),
+        "bcw_index_compact": (C.c_int, [vp, C.c_int]),
         "bcw_index_apply": (C.c_int, [vp, C.c_uint64, vp, u64p, u8p, u64p, u64p, u64p]),
         "bcw_index_apply_stat": (C.c_int, [vp, C.c_uint64, vp, u64p, u8p, u64p, u64p, u64p, u8p, u64p, u64p]),
         "bcw_index_clear": (C.c_int, [vp]),

@@ -11,7 +11,10 @@
 // map.go:395-420) is not restated -- the device index holds every key (capacity grows instead).
 //
 // Layout (HBM): an open-addressing slot table (64 B slots, power-of-two capacity, linear probing from
-// the hash) and a grow-only key arena of {hash, length, key bytes padded to 16} entries.
+// the hash) and a key arena of {hash, length, key bytes padded to 16} entries. Between rebuilds both only fill
+// up: a removed key (Delete, or an eviction by the capacity bound) leaves a dead slot and a dead arena entry, and
+// a live-only rebuild (k_ix_compact: off the batch path, run by the host when half the claimed slots are dead, or
+// on request, bcw_index_compact) gives both back.
 // A batch of operations (host-supplied, or every delivered row of a decoded record / hint table) runs
 // as five stream-ordered launches, so every cross-workgroup hand-off is a kernel boundary:
 //   k_ix_keys   one lane per op: murmur3 over the merged key's 16 B chunks (gathered from the WAL segment
@@ -55,8 +58,10 @@ constexpr uint64_t kProv = 1ull << 63;  // provisional slot reference (claim -> 
 
 // device counters (C_NEED: arena bytes the rows of a decoded table would take, k_ix_need)
 // C_EVICTED / C_EVICTED_BYTES: keys evicted by the capacity bound (k_ix_evict) and the sum of their value sizes
+// C_R_*: the counters of a live-only rebuild in progress (k_ix_compact): arena bytes and slots of the new table,
+// and its failure flag; k_ix_adopt makes them the index's once the rebuild is known to be whole
 enum { C_ARENA = 0, C_SLOTS = 1, C_LIVE = 2, C_OVERFLOW = 3, C_NIN = 4, C_DONE = 5, C_FAIL = 6, C_NEED = 7,
-       C_EVICTED = 8, C_EVICTED_BYTES = 9, C_NUM = 10 };
+       C_EVICTED = 8, C_EVICTED_BYTES = 9, C_R_ARENA = 10, C_R_SLOTS = 11, C_R_FAIL = 12, C_NUM = 13 };
 
 // op sources
 enum { SRC_FLAT = 0, SRC_RECORD = 1, SRC_HINT = 2 };
@@ -582,6 +587,82 @@ __global__ __launch_bounds__(256) void k_ix_rehash(const Slot* __restrict__ old,
   }
 }
 
+// ---- reclaim: rebuild the table and the arena from the live keys only ---------------------------------
+// A removed key (Delete, k_ix_evict) keeps its slot and its arena entry: k_ix_claim only claims empty slots, and the
+// arena only appends. This pass gives both back. One lane per old slot; a live slot (soft-deleted keys are live)
+// takes a fresh arena entry (wave_alloc on the rebuild's own counter: arena order is unobservable), copies its
+// {hash, length, padded key} entry as 16 B chunks and inserts itself into the zeroed new table as k_ix_rehash does,
+// with its sequence number (the clock of the capacity bound) and value unchanged. Dead slots are dropped, so the
+// new probe chains hold live keys only. The counters go to C_R_*; the host adopts them (k_ix_adopt) after it has
+// seen that nothing failed, and keeps the old buffers otherwise.
+
+// arena bytes the live keys' entries take (16 B header + the key padded to 16, as k_ix_commit lays them out)
+__global__ __launch_bounds__(256) void k_ix_live_bytes(const Slot* __restrict__ slots, uint64_t cap,
+                                                       const uint8_t* __restrict__ arena, uint64_t arena_cap,
+                                                       uint64_t* __restrict__ out) {
+  const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
+  uint64_t b = 0;
+  if (i < cap && slots[i].kref && slots[i].live && slots[i].kref - 1 + 16 <= arena_cap)
+    b = 16ull + (((uint64_t)*reinterpret_cast<const uint32_t*>(arena + (slots[i].kref - 1) + 8) + 15) & ~15ull);
+  for (int d = 32; d >= 1; d >>= 1) b += __shfl_xor(b, d, 64);
+  if ((threadIdx.x & 63u) == 0 && b) atomicAdd(reinterpret_cast<unsigned long long*>(out), (unsigned long long)b);
+}
+
+__global__ __launch_bounds__(256) void k_ix_compact(const Slot* __restrict__ old, uint64_t old_cap,
+                                                    const uint8_t* __restrict__ old_arena, uint64_t old_arena_cap,
+                                                    Slot* __restrict__ nw, uint64_t mask, uint8_t* __restrict__ arena,
+                                                    uint64_t arena_cap, uint64_t* __restrict__ cnt) {
+  const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
+  Slot S{};
+  if (i < old_cap) S = old[i];
+  bool act = S.kref != 0 && S.live != 0;
+  uint64_t esz = 0;
+  if (act) {
+    // the entry lies inside the old arena (always, for a consistent index: checked, not assumed, before it is read)
+    const uint64_t src = S.kref - 1;
+    bool in = (S.kref & kProv) == 0 && (src & 15u) == 0 && src + 16 <= old_arena_cap;
+    if (in) {
+      esz = 16ull + (((uint64_t)*reinterpret_cast<const uint32_t*>(old_arena + src + 8) + 15) & ~15ull);
+      in = src + esz <= old_arena_cap;
+    }
+    if (!in) {
+      atomicOr(reinterpret_cast<unsigned long long*>(&cnt[C_R_FAIL]), 1ull);
+      act = false;
+      esz = 0;
+    }
+  }
+  const uint64_t a = wave_alloc(&cnt[C_R_ARENA], esz);
+  (void)wave_alloc(&cnt[C_R_SLOTS], act ? 1ull : 0ull);
+  if (!act) return;
+  if (a + esz > arena_cap) {  // the host sizes the new arena for the live entries; never expected
+    atomicOr(reinterpret_cast<unsigned long long*>(&cnt[C_R_FAIL]), 1ull);
+    return;
+  }
+  const uint4* __restrict__ s = reinterpret_cast<const uint4*>(old_arena + (S.kref - 1));
+  uint4* __restrict__ d = reinterpret_cast<uint4*>(arena + a);
+  for (uint64_t c = 0; c < esz / 16; ++c) d[c] = s[c];
+  uint64_t j = S.hash & mask;
+  for (uint64_t probe = 0; probe <= mask; ++probe, j = (j + 1) & mask) {
+    if (atomicCAS(reinterpret_cast<unsigned long long*>(&nw[j].kref), 0ull, (unsigned long long)(a + 1)) == 0) {
+      nw[j].seq = S.seq;
+      nw[j].hash = S.hash;
+      nw[j].fid = S.fid;
+      nw[j].off = S.off;
+      nw[j].size = S.size;
+      nw[j].live = 1;
+      return;
+    }
+  }
+  atomicOr(reinterpret_cast<unsigned long long*>(&cnt[C_R_FAIL]), 2ull);  // no empty slot; never expected
+}
+
+// the rebuilt table's counters become the index's: every claimed slot is live
+__global__ void k_ix_adopt(uint64_t* __restrict__ cnt) {
+  cnt[C_ARENA] = cnt[C_R_ARENA];
+  cnt[C_SLOTS] = cnt[C_R_SLOTS];
+  cnt[C_LIVE] = cnt[C_R_SLOTS];
+}
+
 // ---- export of the live entries (the Go shim loads them into its ShardMap after a GPU rebuild) --------
 // fids (sorted, nf > 0): only entries whose value fid is one of them (the slice of the index that points into
 // a set of WAL files: the compaction fan-out's filter snapshot)
@@ -665,7 +746,8 @@ __global__ __launch_bounds__(256) void k_ix_export(const Slot* __restrict__ slot
 // than its limit evicts its entries of smallest sequence number (exact LRU order, every entry sampled) until it holds
 // its limit. One workgroup per shard: count its live keys, radix-select (11-bit digits over npass passes) the
 // (n - limit)-th smallest sequence number T (sequence numbers are unique), then evict every entry with seq <= T (live
-// = 0, as Delete: the slot stays claimed). The evicted keys and their value sizes are counted (C_EVICTED*), the
+// = 0, as Delete: the slot and the key's arena entry stay dead until the next live-only rebuild, k_ix_compact, which
+// the host runs once half the claimed slots are dead, so the bound limits HBM use too). The evicted keys and their value sizes are counted (C_EVICTED*), the
 // WriteStat of an eviction (index.go:144-165 reports the evicted value from Set's eviction path).
 __global__ __launch_bounds__(1024) void k_ix_evict(Slot* __restrict__ slots, uint64_t cap, uint64_t lim,
                                                    uint64_t* __restrict__ cnt, uint32_t npass) {
@@ -803,18 +885,69 @@ int ix_grow(bcw_index* x, uint64_t slots, uint64_t arena) {
   return BCW_OK;
 }
 
-// make room for a batch of n ops whose arena entries total at most `arena_bytes`
+// rebuild the index from its live keys only (k_ix_compact) into a table of ncap slots and an arena of narena bytes,
+// both large enough for them; the old buffers are freed after the stream sync, as in ix_grow. On an error the index
+// is left as it was.
+int ix_compact(bcw_index* x, uint64_t ncap, uint64_t narena) {
+  hipStream_t st = x->ctx->cur;
+  Slot* ns = nullptr;
+  uint8_t* na = nullptr;
+  if (hipMalloc(&ns, ncap * sizeof(Slot)) != hipSuccess || hipMalloc(&na, narena) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(ns);
+    return BCW_E_NOMEM;
+  }
+  uint64_t c[C_NUM];
+  bool ok = hipMemsetAsync(ns, 0, ncap * sizeof(Slot), st) == hipSuccess &&
+            hipMemsetAsync(x->cnt + C_R_ARENA, 0, 3 * sizeof(uint64_t), st) == hipSuccess;  // C_R_ARENA, _SLOTS, _FAIL
+  if (ok)
+    k_ix_compact<<<(uint32_t)((x->cap + 255) / 256), 256, 0, st>>>(x->slots, x->cap, x->arena, x->arena_cap, ns,
+                                                                   ncap - 1, na, narena, x->cnt);
+  ok = ok && hipGetLastError() == hipSuccess && ix_sync_counters(x, c) == BCW_OK && c[C_R_FAIL] == 0;
+  if (ok) {
+    k_ix_adopt<<<1, 1, 0, st>>>(x->cnt);
+    ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipFree(ns);
+    (void)hipFree(na);
+    return BCW_E_HIP;
+  }
+  (void)hipFree(x->slots);
+  (void)hipFree(x->arena);
+  x->slots = ns;
+  x->cap = ncap;
+  x->arena = na;
+  x->arena_cap = narena;
+  x->slots_ub = c[C_R_SLOTS];
+  x->arena_ub = c[C_R_ARENA];
+  return BCW_OK;
+}
+
+// make room for a batch of n ops whose arena entries total at most `arena_bytes`. When the batch does not fit the
+// host bounds, the counters are read; if at least half the claimed slots are dead by then, the index is first rebuilt
+// from its live keys at the capacities it has (ix_compact: O(capacity), paid for by the >= 0.35 * capacity removals
+// since the last rebuild or growth -- amortised constant work per removal, as doubling is per insert), and it grows
+// only if the batch still does not fit. A batch that fits costs no sync and no launch here.
 int ix_room(bcw_index* x, uint64_t n, uint64_t arena_bytes) {
-  const bool fits = (double)(x->slots_ub + n) <= kMaxLoad * (double)x->cap && x->arena_ub + arena_bytes <= x->arena_cap;
-  if (!fits) {
+  const auto fits = [&] {
+    return (double)(x->slots_ub + n) <= kMaxLoad * (double)x->cap && x->arena_ub + arena_bytes <= x->arena_cap;
+  };
+  if (!fits()) {
     uint64_t c[C_NUM];
     int rc = ix_sync_counters(x, c);
     if (rc != BCW_OK) return rc;
     if (c[C_OVERFLOW]) return BCW_E_CAPACITY;  // a previous batch overflowed: the index is inconsistent
     x->slots_ub = c[C_SLOTS];
     x->arena_ub = c[C_ARENA];
-    rc = ix_grow(x, x->slots_ub + n, x->arena_ub + arena_bytes);
-    if (rc != BCW_OK) return rc;
+    if (c[C_SLOTS] > 0 && c[C_SLOTS] - c[C_LIVE] >= c[C_SLOTS] / 2) {
+      rc = ix_compact(x, x->cap, x->arena_cap);
+      if (rc != BCW_OK) return rc;
+    }
+    if (!fits()) {
+      rc = ix_grow(x, x->slots_ub + n, x->arena_ub + arena_bytes);
+      if (rc != BCW_OK) return rc;
+    }
   }
   if (n > x->op_cap) {
     (void)hipStreamSynchronize(x->ctx->cur);
@@ -1048,6 +1181,27 @@ int bcw_index_set_limit(bcw_index* x, uint64_t limited) {
   x->limited = limited;
   ix_bound(x);  // an index already past the new bound is brought within it at once
   return hipGetLastError() == hipSuccess && hipStreamSynchronize(x->ctx->cur) == hipSuccess ? BCW_OK : BCW_E_HIP;
+}
+
+int bcw_index_compact(bcw_index* x, int shrink) {
+  if (!x) return BCW_E_INVAL;
+  DeviceGuard dg(x->ctx->device);
+  if (!dg.ok) return BCW_E_HIP;
+  hipStream_t st = x->ctx->cur;
+  uint64_t ncap = x->cap, narena = x->arena_cap;
+  if (shrink && hipMemsetAsync(x->cnt + C_R_ARENA, 0, sizeof(uint64_t), st) != hipSuccess) return BCW_E_HIP;
+  if (shrink)
+    k_ix_live_bytes<<<(uint32_t)((x->cap + 255) / 256), 256, 0, st>>>(x->slots, x->cap, x->arena, x->arena_cap,
+                                                                      x->cnt + C_R_ARENA);
+  uint64_t c[C_NUM];
+  const int rc = hipGetLastError() == hipSuccess ? ix_sync_counters(x, c) : BCW_E_HIP;
+  if (rc != BCW_OK) return rc;
+  if (c[C_OVERFLOW]) return BCW_E_CAPACITY;  // the index is inconsistent
+  if (shrink) {
+    ncap = std::min(ncap, pow2_at_least((uint64_t)((double)c[C_LIVE] / kMaxLoad) + 1));
+    narena = std::min(narena, std::max<uint64_t>(c[C_R_ARENA], 1 << 20));
+  }
+  return ix_compact(x, ncap, narena);
 }
 
 int bcw_index_apply_stat(bcw_index* x, uint64_t n, const uint8_t* h_keys, const uint64_t* h_key_off,

@@ -75,7 +75,10 @@ class Index:
 
     def close(self):
         if self._h:
-            L.lib.bcw_index_destroy(self._h)
+            # bcw_index_destroy syncs the context's stream: an index that outlived its context (closed first, e.g.
+            # at interpreter exit) must not touch it
+            if self.ctx.handle:
+                L.lib.bcw_index_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -180,6 +183,14 @@ class Index:
         rc = L.lib.bcw_index_set_limit(self._h, limited)
         if rc != 0:
             raise RuntimeError(f"bcw_index_set_limit: {L.lib.bcw_strerror(rc).decode()}")
+
+    def compact(self, shrink: bool = False):
+        """give back the slots and key bytes of removed (deleted, evicted) keys: rebuild the table and the arena
+        from the live keys only (bcw_index_compact). shrink: also reduce both capacities to what the live keys need
+        (at least 1024 slots and 1 MiB). Batches do this by themselves once half the claimed slots are dead."""
+        rc = L.lib.bcw_index_compact(self._h, int(bool(shrink)))
+        if rc != 0:
+            raise RuntimeError(f"bcw_index_compact: {L.lib.bcw_strerror(rc).decode()}")
 
     def export(self, fids=None) -> dict:
         """every live entry: {merged key: (fid, off, size)}; fids: only entries whose value fid is one of them

@@ -368,7 +368,7 @@ typedef struct bcw_index_result {
 
 typedef struct bcw_index_info {
   uint64_t live;          /* keys present (Get finds them, soft-deleted included) */
-  uint64_t slots_used;    /* slots claimed (live + deleted keys) */
+  uint64_t slots_used;    /* slots claimed (live keys + keys removed since the last rebuild, bcw_index_compact) */
   uint64_t slot_capacity;
   uint64_t arena_used;    /* key arena bytes */
   uint64_t arena_capacity;
@@ -389,8 +389,21 @@ int bcw_index_stats(bcw_index* ix, bcw_index_info* out);
  * expire is the sequence number of the last op that set it, and after every batch (apply, put / recover of a
  * decoded table, the fan-out's ordered puts) each shard over its limit evicts its least recently set entries until
  * it holds its limit. A Get of an evicted key fails (ErrKeyNotFound), so the compaction filter drops its rows. The
- * evictions are counted in bcw_index_info (evicted, evicted_bytes). Applies the bound at once. */
+ * evictions are counted in bcw_index_info (evicted, evicted_bytes). Applies the bound at once.
+ * The bound limits HBM use as well as visible keys: an evicted (or deleted) key's slot and key bytes stay dead only
+ * until the next live-only rebuild, which a batch that does not fit runs by itself once half the claimed slots are
+ * dead (before it would grow the index), so a bounded index under any churn stays within a constant factor of what
+ * its bound needs. */
 int bcw_index_set_limit(bcw_index* ix, uint64_t limited);
+/* Reclaim what removed keys used, now: rebuild the slot table and the key arena from the live keys only (soft-deleted
+ * keys are live). Every Get, the export and the eviction order are unchanged; afterwards slots_used == live and
+ * arena_used is the live keys' entries (16 + the key length rounded up to 16, each). shrink == 0 keeps both
+ * capacities; shrink != 0 also reduces the slot table to the smallest power of two that holds the live keys at the
+ * table's maximum load (0.7; never below 1024 slots) and the arena to max(live entry bytes, 1 MiB). Synchronous; like
+ * every index call, one caller at a time on the index (the buffers are swapped as a growth swaps them). Returns
+ * BCW_E_CAPACITY when the overflow flag is set (the index is inconsistent), BCW_E_NOMEM / BCW_E_HIP with the index
+ * left as it was. */
+int bcw_index_compact(bcw_index* ix, int shrink);
 /* Index.Put / Delete / SoftDelete of n merged keys (host arrays; key i = h_keys[h_key_off[i], h_key_off[i+1]),
  * h_ops[i] = BCW_IDX_*), applied in order (the Go shim mirrors DBImpl.writeIndex, db_impl.go:433-452).
  * Synchronous. */
