@@ -107,12 +107,12 @@ __device__ __forceinline__ uint32_t wg256_excl_scan(uint32_t v, uint32_t* sm4, u
 }
 
 // ------------------------------------------------------------------------------------------
-// Single-pass header chase with a decoupled look-back over workgroups: every lane of a one-wave
-// workgroup chases one block (keeping its first kChaseHold headers in LDS), the wave scans the counts,
+// Single-pass header chase with a decoupled look-back over workgroups: every lane of the workgroup's first
+// wave chases one block (keeping its first kChaseHold headers in LDS), the wave scans the counts,
 // publishes its aggregate and walks back over earlier workgroups' published values for its fragment
 // base, then writes the fragment table (a block with more headers chases its tail again; the lines are
 // cache-resident by then). A workgroup only waits on lower workgroup ids (dispatched before it). Look-back words:
-// epoch << 40 | flag << 38 | count (flag 1: aggregate, 2: inclusive prefix). One wave per workgroup spreads the blocks over every CU: the chase is a chain
+// epoch << 40 | flag << 38 | count (flag 1: aggregate, 2: inclusive prefix). One chasing wave per workgroup spreads the blocks over every CU: the chase is a chain
 // of scattered header reads, bound by latency and by each CU's address-processing rate.
 //
 // The chase is the iterator's header loop (wal_iterator.go:45-77: the block's buffer is
@@ -289,8 +289,16 @@ __device__ __forceinline__ ClassW class_weights(uint32_t xw) {
 // ABL: ablation bits for tools/kbench only (0 in the product): 1 no predecessor sum, 2 no table writes,
 // 16 phase cycles (chase, sum, writes; s_memtime) summed into misc[7..9], 32 per-workgroup wall-clock stamps (entry,
 // chase end, sum end, end) into lbe[4 wg ..] (kbench passes a buffer of its own; direct-sum sizes only)
-template <int ABL = 0>
-__global__ __launch_bounds__(64) void k_chase(const uint8_t* __restrict__ seg, uint64_t seg_len, uint32_t start_off,
+//
+// The workgroup is WAVES waves over the same 64 blocks. Wave 0 chases (one block per lane), scans, publishes and sums
+// the predecessors: the chain every other workgroup waits on. The helper waves park at a barrier until the chase has
+// ended and do, while wave 0 waits for the predecessors, what needs no base: the held headers' check words and the
+// wave boundaries that lie among the held headers (block and header count of each, boundary-major). After a second
+// barrier, where wave 0 hands each block's base over in LDS, all waves store. Helpers wait only at the barriers.
+constexpr int kChaseWaves = 4;
+constexpr int kBoundHeld = 4;  // batches of 64 wave boundaries resolved before the sum (config B has 8 per workgroup)
+template <int ABL = 0, int WAVES = kChaseWaves>
+__global__ __launch_bounds__(WAVES * 64) void k_chase(const uint8_t* __restrict__ seg, uint64_t seg_len, uint32_t start_off,
                                               uint64_t nblocks, uint32_t* __restrict__ fbase,
                                               uint32_t* __restrict__ rbase, uint2* __restrict__ bsum,
                                               Frag* __restrict__ frags, uint4* __restrict__ srec, uint64_t frag_cap,
@@ -308,9 +316,20 @@ __global__ __launch_bounds__(64) void k_chase(const uint8_t* __restrict__ seg, u
   constexpr int kHold = (ABL & 256) ? 16 : kChaseHold;
   __shared__ uint32_t s_hold[kHold][2][64];
   __shared__ uint8_t s_type[kHold][64];
-  const uint32_t lane = threadIdx.x;
+  // each block's header count (after the chase) and first fragment (after the sum), from wave 0 to the others; the
+  // boundaries resolved before the sum (block | headers before it << 8, 0xffff: none): 37.25 KiB in all
+  __shared__ uint32_t s_n[64];
+  __shared__ uint64_t s_g0[64];
+  __shared__ uint16_t s_bnd[kBoundHeld * 64];
+  static_assert(WAVES >= 2 && WAVES <= 16, "wave 0 and at least one helper");
+  static_assert(sizeof(s_hold) + sizeof(s_type) + sizeof(s_n) + sizeof(s_g0) + sizeof(s_bnd) <= 44 * 1024,
+                "a k_chase workgroup fits beside a k_crc workgroup");
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform within the wave)
+  constexpr uint32_t kBndWave = WAVES - 1;                // the helper that resolves and writes the wave boundaries
+  constexpr uint32_t kChkWaves = WAVES > 2 ? WAVES - 2 : 1;  // helpers 1..kChkWaves compute the check words
   // k_crc's per-XCD split (XBal): the range weight of each class, requested now, used after the chase
-  const uint32_t xw = lane < 8u ? (xb_on ? xb->w[lane] : 65536u) : 0u;
+  const uint32_t xw = (wv == 0 || wv == kBndWave) && lane < 8u ? (xb_on ? xb->w[lane] : 65536u) : 0u;
   const uint64_t tc0 = (ABL & 16) ? __builtin_amdgcn_s_memtime() : 0;
   if ((ABL & 32) && threadIdx.x == 0) lbe[4 * blockIdx.x] = wall_clock64();
   // the workgroup id orders the look-back: workgroups are dispatched in id order (within each XCD), so one only waits
@@ -329,31 +348,8 @@ __global__ __launch_bounds__(64) void k_chase(const uint8_t* __restrict__ seg, u
   // record-state summary of the block (see kSumHasE) and its first unknown-type fragment
   uint32_t ne = 0, tacc = 0, tnz = 0xffffu, tst = 0, badk = 0xffffffffu;
   uint32_t hres = 0;  // where the first header past the held ones starts (the table pass resumes there)
-  const uint32_t n = chase_block(seg, seg_len, boff, bufsize,
-                                 [&](uint32_t k, uint32_t start, uint32_t len, uint32_t crc, uint32_t type) {
-                                   if (k < (uint32_t)kHold) {
-                                     s_hold[k][0][lane] = crc;
-                                     s_hold[k][1][lane] = start | (len << 16);
-                                     s_type[k][lane] = (uint8_t)type;
-                                   }
-                                   if (k == (uint32_t)kHold - 1u) hres = start + len;
-                                   if (type == BCW_RECORD_FULL || type == BCW_RECORD_LAST) {
-                                     ++ne;
-                                     tacc = 0;
-                                     tnz = 0xffffu;
-                                   } else {
-                                     if (len > 0 && tnz == 0xffffu) { tnz = k; tst = start; }
-                                     tacc += len;
-                                     if ((type < BCW_RECORD_FULL || type > BCW_RECORD_LAST) && badk == 0xffffffffu) badk = k;
-                                   }
-                                 });
-  const uint64_t tc1 = (ABL & 16) ? __builtin_amdgcn_s_memtime() : 0;
-  if ((ABL & 32) && lane == 0) lbe[4 * wg + 1] = wall_clock64();
-  if (wg == 0 && lane == 0) xb->on = xb_on;
-  const uint32_t incl = wave_add_scan(n, lane);
-  const uint32_t tot = __builtin_amdgcn_readlane(incl, 63);
-  const uint32_t incl_e = wave_add_scan(ne, lane);
-  const uint32_t tot_e = __builtin_amdgcn_readlane(incl_e, 63);
+  uint32_t n = 0, incl = 0, tot = 0, incl_e = 0, tot_e = 0;
+  uint64_t tc1 = 0;
   // publish, then sum the predecessors. Up to kDirect workgroups (a 2 GiB segment) every workgroup publishes
   // only its aggregate (fragment and Full/Last counts packed: at most 64 * 4681 < 2^19 each) and sums all of its
   // predecessors' at once (up to kDirect / 64 loads per lane, all in flight); beyond that, the decoupled look-back
@@ -361,174 +357,272 @@ __global__ __launch_bounds__(64) void k_chase(const uint8_t* __restrict__ seg, u
   // inclusive prefixes would otherwise serialize the workgroups.
   const uint64_t tag = epoch << 40;
   const uint64_t nwg_all = (nblocks + 63) / 64;
+  const bool direct = nwg_all <= (uint64_t)direct_max;  // direct_max <= kDirect (bcw_ctx_set_option)
   const bool force = wg + 1 == test_abort_wg;  // BCW_OPT_TEST_ABORT_WAIT (wave-uniform)
-  uint64_t excl = 0, excl_e = 0;
-  const uint32_t nh = n < (uint32_t)kHold ? n : (uint32_t)kHold;
-  // the held headers' check words J (their initc[len] loads issued 16 at a time), computed while the predecessors'
-  // counts are awaited: only the stores are left for after the sum (s_hold[k][0] holds J from here on)
-  auto held_checks = [&]() {
-    if (ABL & 2) return;
-    constexpr uint32_t kWb = 16;
-    static_assert(kHold % kWb == 0, "held-header batches stay inside s_hold");
-    for (uint32_t k0 = 0; k0 < nh; k0 += kWb) {
-      uint32_t ic[kWb];
-#pragma unroll
-      for (uint32_t q = 0; q < kWb; ++q) ic[q] = initc[k0 + q < nh ? s_hold[k0 + q][1][lane] >> 16 : 0u];
-#pragma unroll
-      for (uint32_t q = 0; q < kWb; ++q)
-        if (k0 + q < nh) s_hold[k0 + q][0][lane] = check_word(s_hold[k0 + q][0][lane], ic[q]);
-    }
-  };
-  if (ABL & 1) {
-    held_checks();
-  } else if (nwg_all <= (uint64_t)direct_max) {  // direct_max <= kDirect (bcw_ctx_set_option)
-    if (lane == 0)
-      __hip_atomic_store(&lb[wg], tag | (kLbAgg << 38) | tot | ((uint64_t)tot_e << 19), __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    uint64_t v[kDirect / 64];
-#pragma unroll
-    for (int k = 0; k < kDirect / 64; ++k) {
-      const uint64_t q = lane + 64u * k;
-      v[k] = q < wg ? __hip_atomic_load(&lb[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : tag;
-    }
-    held_checks();
-    // the words not yet published are polled again all together (one round trip per poll, not one per word: polled
-    // one word at a time, the sum ended ~5 us after the last chase on B, kbench k_chase stamps)
-    Spin sp;  // bounded (BCW_ERR_INTERNAL)
-    if (force) sp.lim = 0;
-    for (;;) {
-      bool wait = force;
-#pragma unroll
-      for (int k = 0; k < kDirect / 64; ++k) wait |= (v[k] >> 40) != epoch;
-      if (!__builtin_amdgcn_readfirstlane((uint32_t)(__ballot(wait) != 0ull))) break;
-      if (!sp.go(misc, 9)) {
-#pragma unroll
-        for (int k = 0; k < kDirect / 64; ++k)
-          if ((v[k] >> 40) != epoch) v[k] = 0;
-        break;
+  if (wv == 0) {
+    n = chase_block(seg, seg_len, boff, bufsize,
+                    [&](uint32_t k, uint32_t start, uint32_t len, uint32_t crc, uint32_t type) {
+                      if (k < (uint32_t)kHold) {
+                        s_hold[k][0][lane] = crc;
+                        s_hold[k][1][lane] = start | (len << 16);
+                        s_type[k][lane] = (uint8_t)type;
+                      }
+                      if (k == (uint32_t)kHold - 1u) hres = start + len;
+                      if (type == BCW_RECORD_FULL || type == BCW_RECORD_LAST) {
+                        ++ne;
+                        tacc = 0;
+                        tnz = 0xffffu;
+                      } else {
+                        if (len > 0 && tnz == 0xffffu) { tnz = k; tst = start; }
+                        tacc += len;
+                        if ((type < BCW_RECORD_FULL || type > BCW_RECORD_LAST) && badk == 0xffffffffu) badk = k;
+                      }
+                    });
+    s_n[lane] = n;
+    tc1 = (ABL & 16) ? __builtin_amdgcn_s_memtime() : 0;
+    if ((ABL & 32) && lane == 0) lbe[4 * wg + 1] = wall_clock64();
+    if (wg == 0 && lane == 0) xb->on = xb_on;
+    incl = wave_add_scan(n, lane);
+    tot = __builtin_amdgcn_readlane(incl, 63);
+    incl_e = wave_add_scan(ne, lane);
+    tot_e = __builtin_amdgcn_readlane(incl_e, 63);
+    if (!(ABL & 1) && lane == 0) {
+      if (direct) {
+        __hip_atomic_store(&lb[wg], tag | (kLbAgg << 38) | tot | ((uint64_t)tot_e << 19), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+      } else {
+        const uint64_t fl = (wg == 0 ? kLbInc : kLbAgg) << 38;
+        __hip_atomic_store(&lb[wg], tag | fl | tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&lbe[wg], tag | fl | tot_e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
+    }
+  }
+  __syncthreads();  // the chase has ended: s_hold, s_type and s_n are the helpers' to read
+  uint64_t excl = 0, excl_e = 0;
+  const uint32_t nh = min(s_n[lane], (uint32_t)kHold);
+  // k_crc's wave ranges, balanced by bytes: wave w streams the fragments whose header lies in [P_w, P_w+1)
+  // (positions after start_off), so wstart[w] = the first fragment whose header is at or after P_w: its block's
+  // first fragment plus the block's headers before P_w. Range r (k_crc's workgroup r, class r % 8) has its class's
+  // weight (WavePart). A block owns the boundaries from its first byte up to its last (the segment's last block:
+  // every one left, up to P_nwaves = L, which lies at its span's end when L is a multiple of 32 KiB).
+  // (Whole blocks per wave left 7 of config B's 4096 waves with 9 blocks instead of 8: they ended ~20 us after the
+  // median wave, kbench timelines.)
+  // Boundary-major, for the whole workgroup: lane i of a batch takes boundary base + i, finds its block and searches
+  // that block's held headers. 0: past the workgroup's span; 1: e = block | headers before it << 8; 2: it lies past
+  // the last held header of a block with more (the block's own lane writes it when it chases that tail again).
+  const uint64_t L = seg_len - start_off;
+  const uint64_t rel0 = wg * 64u * (uint64_t)kBlock;
+  const bool last_wg = wg * 64u + 64u >= nblocks;
+  const uint32_t nbl = last_wg ? (uint32_t)(nblocks - wg * 64u) : 64u;
+  auto resolve = [&](const WavePart& wp, uint64_t w, uint32_t& e) __attribute__((always_inline)) -> uint32_t {
+    if (w > nwaves) return 0u;
+    const uint64_t p = wp.P(w) - rel0;  // (P(w) >= rel0: w starts at first_at(rel0))
+    if (!last_wg && p > 64u * (uint64_t)kBlock - 1u) return 0u;
+    const uint32_t bl = min((uint32_t)min(p / kBlock, (uint64_t)63u), nbl - 1u);
+    const uint64_t bw = p - (uint64_t)bl * kBlock;  // block-relative
+    const uint32_t nb = s_n[bl], nhb = min(nb, (uint32_t)kHold);
+    uint32_t cnt = 0;  // the held headers that start before bw (their positions ascend)
+#pragma unroll
+    for (uint32_t s = kHold; s >= 1u; s >>= 1) {
+      const uint32_t i = cnt + s - 1u;
+      if (i < nhb && (uint64_t)((s_hold[i][1][bl] & 0xffffu) - kHdr) < bw) cnt += s;
+    }
+    if (cnt == (uint32_t)kHold && nb > (uint32_t)kHold) return 2u;
+    e = bl | cnt << 8;
+    return 1u;
+  };
+  uint64_t w_lo = 0;       // the workgroup's first boundary
+  uint32_t bnd_done = 0;   // batches in s_bnd, | 0x100: they are all
+  if (wv == 0) {
+    if (ABL & 1) {  // (kbench: no predecessor sum)
+    } else if (direct) {
+      uint64_t v[kDirect / 64];
 #pragma unroll
       for (int k = 0; k < kDirect / 64; ++k) {
         const uint64_t q = lane + 64u * k;
-        if ((v[k] >> 40) != epoch) v[k] = __hip_atomic_load(&lb[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        v[k] = q < wg ? __hip_atomic_load(&lb[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : tag;
+      }
+      // the words not yet published are polled again all together (one round trip per poll, not one per word: polled
+      // one word at a time, the sum ended ~5 us after the last chase on B, kbench k_chase stamps)
+      Spin sp;  // bounded (BCW_ERR_INTERNAL)
+      if (force) sp.lim = 0;
+      for (;;) {
+        bool wait = force;
+#pragma unroll
+        for (int k = 0; k < kDirect / 64; ++k) wait |= (v[k] >> 40) != epoch;
+        if (!__builtin_amdgcn_readfirstlane((uint32_t)(__ballot(wait) != 0ull))) break;
+        if (!sp.go(misc, 9)) {
+#pragma unroll
+          for (int k = 0; k < kDirect / 64; ++k)
+            if ((v[k] >> 40) != epoch) v[k] = 0;
+          break;
+        }
+#pragma unroll
+        for (int k = 0; k < kDirect / 64; ++k) {
+          const uint64_t q = lane + 64u * k;
+          if ((v[k] >> 40) != epoch) v[k] = __hip_atomic_load(&lb[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+      uint64_t c = 0, ce = 0;
+#pragma unroll
+      for (int k = 0; k < kDirect / 64; ++k) {
+        const uint64_t q = lane + 64u * k;
+        if (q < wg) {
+          c += v[k] & 0x7ffffu;
+          ce += (v[k] >> 19) & 0x7ffffu;
+        }
+      }
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) {
+        c += (uint64_t)__shfl_xor((long long)c, d, 64);
+        ce += (uint64_t)__shfl_xor((long long)ce, d, 64);
+      }
+      excl = c;
+      excl_e = ce;
+    } else {
+      // both counts walk back together; each stops at its own nearest inclusive prefix (the two words of a
+      // predecessor turn inclusive one after the other)
+      bool dn = false, de = false;
+      for (uint64_t top = wg; top > 0 && !(dn && de);) {  // predecessors [top - 64, top)
+        const uint64_t q = top - 1 - lane;  // lane 0: the nearest
+        uint64_t vn = 0, ve = 0;
+        if (top > lane) {
+          Spin sp;
+          if (force) sp.lim = 0;
+          if (!dn)
+            while (((vn = __hip_atomic_load(&lb[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 40) != epoch ||
+                   force)
+              if (!sp.go(misc, 10)) { vn = 0; break; }
+          if (!de)
+            while (((ve = __hip_atomic_load(&lbe[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 40) != epoch ||
+                   force)
+              if (!sp.go(misc, 11)) { ve = 0; break; }
+        }
+        auto step = [&](uint64_t v, bool& done, uint64_t& acc) {
+          if (done) return;
+          const uint64_t inc = __ballot(top > lane && ((v >> 38) & 3u) == kLbInc);
+          const uint32_t stop = inc ? (uint32_t)__builtin_ctzll(inc) : 64u;  // nearest inclusive prefix
+          uint64_t c = (lane <= stop && top > lane) ? (v & kLbMask) : 0ull;
+#pragma unroll
+          for (int d = 32; d >= 1; d >>= 1) c += (uint64_t)__shfl_xor((long long)c, d, 64);
+          acc += c;
+          done = inc != 0;
+        };
+        step(vn, dn, excl);
+        step(ve, de, excl_e);
+        top = top > 64 ? top - 64 : 0;
+      }
+      if (lane == 0 && wg != 0) {
+        __hip_atomic_store(&lb[wg], tag | (kLbInc << 38) | ((excl + tot) & kLbMask), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&lbe[wg], tag | (kLbInc << 38) | ((excl_e + tot_e) & kLbMask), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
       }
     }
-    uint64_t c = 0, ce = 0;
+    s_g0[lane] = excl + incl - n;
+  } else if (!(ABL & 2)) {
+    // the held headers' check words J (their initc[len] loads issued 16 at a time), computed while wave 0 awaits
+    // the predecessors' counts: only the stores are left for after the sum (s_hold[k][0] holds J from here on)
+    if (wv <= kChkWaves) {
+      constexpr uint32_t kWb = 16;
+      static_assert(kHold % kWb == 0, "held-header batches stay inside s_hold");
+      for (uint32_t k0 = kWb * (wv - 1u); k0 < nh; k0 += kWb * kChkWaves) {
+        uint32_t ic[kWb];
 #pragma unroll
-    for (int k = 0; k < kDirect / 64; ++k) {
-      const uint64_t q = lane + 64u * k;
-      if (q < wg) {
-        c += v[k] & 0x7ffffu;
-        ce += (v[k] >> 19) & 0x7ffffu;
+        for (uint32_t q = 0; q < kWb; ++q) ic[q] = initc[k0 + q < nh ? s_hold[k0 + q][1][lane] >> 16 : 0u];
+#pragma unroll
+        for (uint32_t q = 0; q < kWb; ++q)
+          if (k0 + q < nh) s_hold[k0 + q][0][lane] = check_word(s_hold[k0 + q][0][lane], ic[q]);
       }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      c += (uint64_t)__shfl_xor((long long)c, d, 64);
-      ce += (uint64_t)__shfl_xor((long long)ce, d, 64);
-    }
-    excl = c;
-    excl_e = ce;
-  } else {
-    const uint64_t fl = (wg == 0 ? kLbInc : kLbAgg) << 38;
-    if (lane == 0) {
-      __hip_atomic_store(&lb[wg], tag | fl | tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&lbe[wg], tag | fl | tot_e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    held_checks();
-    // both counts walk back together; each stops at its own nearest inclusive prefix (the two words of a
-    // predecessor turn inclusive one after the other)
-    bool dn = false, de = false;
-    for (uint64_t top = wg; top > 0 && !(dn && de);) {  // predecessors [top - 64, top)
-      const uint64_t q = top - 1 - lane;  // lane 0: the nearest
-      uint64_t vn = 0, ve = 0;
-      if (top > lane) {
-        Spin sp;
-        if (force) sp.lim = 0;
-        if (!dn)
-          while (((vn = __hip_atomic_load(&lb[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 40) != epoch || force)
-            if (!sp.go(misc, 10)) { vn = 0; break; }
-        if (!de)
-          while (((ve = __hip_atomic_load(&lbe[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 40) != epoch || force)
-            if (!sp.go(misc, 11)) { ve = 0; break; }
+    if (wv == kBndWave) {  // the first batches of the workgroup's boundaries, kept in LDS until the bases are known
+      const WavePart wp(class_weights(xw), L, nwaves);
+      w_lo = wp.first_at(rel0);
+      for (; bnd_done < (uint32_t)kBoundHeld; ++bnd_done) {
+        uint32_t e = 0;
+        const uint32_t r = resolve(wp, w_lo + 64u * bnd_done + lane, e);
+        if (__ballot(r != 0u) == 0ull) { bnd_done |= 0x100u; break; }
+        s_bnd[64u * bnd_done + lane] = (uint16_t)(r == 1u ? e : 0xffffu);
       }
-      auto step = [&](uint64_t v, bool& done, uint64_t& acc) {
-        if (done) return;
-        const uint64_t inc = __ballot(top > lane && ((v >> 38) & 3u) == kLbInc);
-        const uint32_t stop = inc ? (uint32_t)__builtin_ctzll(inc) : 64u;  // nearest inclusive prefix
-        uint64_t c = (lane <= stop && top > lane) ? (v & kLbMask) : 0ull;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) c += (uint64_t)__shfl_xor((long long)c, d, 64);
-        acc += c;
-        done = inc != 0;
-      };
-      step(vn, dn, excl);
-      step(ve, de, excl_e);
-      top = top > 64 ? top - 64 : 0;
-    }
-    if (lane == 0 && wg != 0) {
-      __hip_atomic_store(&lb[wg], tag | (kLbInc << 38) | ((excl + tot) & kLbMask), __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&lbe[wg], tag | (kLbInc << 38) | ((excl_e + tot_e) & kLbMask), __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-  const uint64_t g0 = excl + incl - n;
   const uint64_t tc2 = (ABL & 16) ? __builtin_amdgcn_s_memtime() : 0;
-  if ((ABL & 32) && lane == 0) lbe[4 * wg + 2] = wall_clock64();
+  if ((ABL & 32) && threadIdx.x == 0) lbe[4 * wg + 2] = wall_clock64();
+  __syncthreads();  // the sum has ended: s_g0 is every wave's to read, and the helpers' LDS results wave 0's
   if (b < nblocks && !(ABL & 2)) {
-    fbase[b] = (uint32_t)(g0 < 0xffffffffull ? g0 : 0xffffffffull);
-    const uint64_t r0 = excl_e + incl_e - ne;
-    rbase[b] = (uint32_t)(r0 < 0xffffffffull ? r0 : 0xffffffffull);
-    bsum[b] = make_uint2(tacc | (tnz << 16), tst | (ne ? kSumHasE : 0u));
-    if (badk != 0xffffffffu)  // the first unknown-type fragment of the segment (reset by the previous finalize)
-      atomicMin(reinterpret_cast<unsigned long long*>(&misc[M_BAD_TYPE]), (unsigned long long)(g0 + badk));
-    // the held headers' entries (their J computed during the wait, held_checks). The block's last fragment is
-    // adjacent to the next block's first when it ends exactly at this full block's end and the next block holds a
-    // header.
+    const uint64_t g0 = s_g0[lane];
+    n = s_n[lane];
+    if (wv == 0) {
+      fbase[b] = (uint32_t)(g0 < 0xffffffffull ? g0 : 0xffffffffull);
+      const uint64_t r0 = excl_e + incl_e - ne;
+      rbase[b] = (uint32_t)(r0 < 0xffffffffull ? r0 : 0xffffffffull);
+      bsum[b] = make_uint2(tacc | (tnz << 16), tst | (ne ? kSumHasE : 0u));
+      if (badk != 0xffffffffu)  // the first unknown-type fragment of the segment (reset by the previous finalize)
+        atomicMin(reinterpret_cast<unsigned long long*>(&misc[M_BAD_TYPE]), (unsigned long long)(g0 + badk));
+    }
+    // the held headers' entries (their J computed during the wait), wave j those with k = j mod WAVES. The block's
+    // last fragment is adjacent to the next block's first when it ends exactly at this full block's end and the next
+    // block holds a header.
     const bool next_hdr = b + 1 < nblocks && seg_len - (boff + kBlock) >= kHdr;
     auto adj = [&](uint32_t k, uint32_t sl_k) { return k + 1u < n || (next_hdr && (sl_k & 0xffffu) + (sl_k >> 16) == kBlock); };
-    // k_crc's wave ranges, balanced by bytes: wave w streams the fragments whose header lies in [P_w, P_w+1)
-    // (positions after start_off), so wstart[w] = the first fragment whose header is at or after P_w. This lane writes the boundaries that fall in its block, walking its headers in order.
-    // (Whole blocks per wave left 7 of config B's 4096 waves with 9 blocks instead of 8: they ended ~20 us after the
-    // median wave, kbench timelines.)
-    // Range r (k_crc's workgroup r, class r % 8) has its class's weight (WavePart). This lane writes the boundaries
-    // that lie in its block: from the first at or after its start while they lie before its end (the segment's last
-    // block: every one left, up to P_nwaves = L, which lies at its span's end when L is a multiple of 32 KiB). (A
-    // second first_at for the block's end cost ~1 us of k_chase's table pass.)
-    const uint64_t L = seg_len - start_off, rel = boff - start_off;
-    const WavePart wp(class_weights(xw), L, nwaves);
-    const uint64_t span = b + 1 == nblocks ? ~0ull : (uint64_t)kBlock - 1;  // the last position it owns
-    uint64_t w = wp.first_at(rel);
-    uint64_t bw = wp.P(w) - rel;  // boundary w, block-relative
-    auto bounds_upto = [&](uint64_t hp, uint64_t idx) __attribute__((always_inline)) {  // boundaries at or before hp: idx
-      const uint64_t h = hp < span ? hp : span;
-      while (w <= nwaves && bw <= h) {
-        wstart[w] = (uint32_t)(idx < 0xffffffffull ? idx : 0xffffffffull);
-        ++w;
-        bw = wp.P(w) - rel;
-      }
-    };
-    for (uint32_t k = 0; k < nh; ++k) {
+    for (uint32_t k = wv; k < nh; k += (uint32_t)WAVES) {
       const uint32_t sl = s_hold[k][1][lane];
       put_frag_J(frags, srec, g0 + k, frag_cap, (uint32_t)b, boff, sl, s_hold[k][0][lane], s_type[k][lane],
                  adj(k, sl));
-      bounds_upto((sl & 0xffffu) - kHdr, g0 + k);
     }
-    if (n > (uint32_t)kHold)  // the tail of a block with more headers than held, chased again from the first of them
+    // the tail of a block with more headers than held, chased again from the first of them by its own lane, which
+    // walks the boundaries past its last held header in header order (a second first_at per block cost ~1 us of the
+    // one-wave table pass: it is paid here only by blocks with a tail)
+    if (wv == 0 && n > (uint32_t)kHold) {
+      const uint64_t rel = boff - start_off;
+      const WavePart wp(class_weights(xw), L, nwaves);
+      const uint64_t span = b + 1 == nblocks ? ~0ull : (uint64_t)kBlock - 1;  // the last position it owns
+      uint64_t w = wp.first_at(rel + (s_hold[kHold - 1][1][lane] & 0xffffu) - kHdr + 1u);
+      uint64_t bw = wp.P(w) - rel;  // boundary w, block-relative
+      auto bounds_upto = [&](uint64_t hp, uint64_t idx) __attribute__((always_inline)) {  // boundaries at or before hp: idx
+        const uint64_t h = hp < span ? hp : span;
+        while (w <= nwaves && bw <= h) {
+          wstart[w] = (uint32_t)(idx < 0xffffffffull ? idx : 0xffffffffull);
+          ++w;
+          bw = wp.P(w) - rel;
+        }
+      };
       chase_block(seg, seg_len, boff, bufsize, [&](uint32_t k, uint32_t start, uint32_t len, uint32_t crc, uint32_t type) {
         put_frag(frags, srec, g0 + k, frag_cap, (uint32_t)b, boff, start, len, crc, type, initc,
                  adj(k, start | (len << 16)));
         bounds_upto(start - kHdr, g0 + k);
       }, hres, (uint32_t)kHold);
-    bounds_upto(~0ull, g0 + n);  // boundaries after the block's last header: the next block's first fragment
+      bounds_upto(~0ull, g0 + n);  // boundaries after the block's last header: the next block's first fragment
+    }
   }
-  if (ABL & 32) {
+  if (wv == kBndWave && !(ABL & 2)) {  // the boundaries among the held headers: those kept in LDS, then the rest
+    auto put = [&](uint64_t w, uint32_t e) {
+      const uint64_t idx = s_g0[e & 0xffu] + (e >> 8);
+      wstart[w] = (uint32_t)(idx < 0xffffffffull ? idx : 0xffffffffull);
+    };
+    for (uint32_t i = 0; i < (bnd_done & 0xffu); ++i) {
+      const uint32_t e = s_bnd[64u * i + lane];
+      if (e != 0xffffu) put(w_lo + 64u * i + lane, e);
+    }
+    if (!(bnd_done & 0x100u)) {
+      const WavePart wp(class_weights(xw), L, nwaves);
+      for (uint64_t base = w_lo + 64u * (uint32_t)kBoundHeld;; base += 64u) {
+        uint32_t e = 0;
+        const uint32_t r = resolve(wp, base + lane, e);
+        if (__ballot(r != 0u) == 0ull) break;
+        if (r == 1u) put(base + lane, e);
+      }
+    }
+  }
+  if (ABL & 48) {  // (kbench) the workgroup's end: every wave's stores
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+  if (wv != 0) return;
+  if (ABL & 32) {
     if (lane == 0) lbe[4 * wg + 3] = wall_clock64();
   }
   if (ABL & 16) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const uint64_t tc3 = __builtin_amdgcn_s_memtime();
     if (lane == 0) {
       atomicAdd(reinterpret_cast<unsigned long long*>(&misc[7]), (unsigned long long)(tc1 - tc0));
@@ -1608,7 +1702,7 @@ hipError_t launch_decode(const uint8_t* d_seg, const bcw_decode_params& p, const
   const uint32_t nb_grid = (uint32_t)(((nblocks + 63) / 64 + 7) / 8 * 8);
   const EmitArgs ea{d_seg, p.seg_len, p, s.frags, s.fbase, s.rbase, s.bsum, t, s.misc, 0u, nullptr};
   pr.begin(K_CHASE, stream, ev);
-  k_chase<0><<<nb_grid, 64, 0, stream>>>(d_seg, p.seg_len, p.start_off, nblocks, s.fbase, s.rbase, s.bsum, s.frags,
+  k_chase<0><<<nb_grid, kChaseWaves * 64, 0, stream>>>(d_seg, p.seg_len, p.start_off, nblocks, s.fbase, s.rbase, s.bsum, s.frags,
                                         s.srec, s.frag_cap, s.lb, s.lbe, s.misc, s.epoch, tabs.initc, s.chase_direct,
                                         s.test_abort_wg, s.wstart, (uint32_t)num_cus * kCrcWaves, s.xbal, s.xbal_on);
   s.test_abort_wg = 0;

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #define CK(x) do { auto e_ = (x); if (e_ != hipSuccess && e_ != 0) { fprintf(stderr, "%s:%d err %d\n", __FILE__, __LINE__, (int)e_); exit(1);} } while (0)
@@ -353,6 +354,74 @@ int main(int argc, char** argv) {
       default: return run(k_crc<0>, cus, ea);
     }
   };
+  // k_chase alone: its ablations, per-workgroup stamps and phase cycles, with WV waves per workgroup
+  auto chase_report = [&](auto wv_c) {
+    constexpr int WV = decltype(wv_c)::value;
+    auto crun = [&](auto kern) {
+      return timeit([&] {
+        kern<<<(uint32_t)((nblocks + 63) / 64), WV * 64, 0, st>>>(d, n, 40, nblocks, s.fbase, s.rbase, s.bsum, s.frags,
+                                                              s.srec, s.frag_cap, s.lb, s.lbe, s.misc, s.epoch,
+                                                              ctx->tabs.initc, s.chase_direct, 0ull, s.wstart,
+                                                              (uint32_t)cus * kCrcWaves, s.xbal, s.xbal_on);
+        ++s.epoch;
+      }, reps, st);
+    };
+    printf("k_chase (%d waves) alone %.4f  no sum %.4f  no writes %.4f  chase only %.4f ms  hold 16: %.4f ms\n", WV, crun(k_chase<0, WV>),
+           crun(k_chase<1, WV>), crun(k_chase<2, WV>), crun(k_chase<3, WV>), crun(k_chase<256, WV>));
+    {
+      uint32_t* pout;
+      CK(hipMalloc(&pout, (nblocks + 64) * 4));
+      const uint32_t pg = (uint32_t)((nblocks + 63) / 64);
+      const float p0 = timeit([&] { k_chase_probe<0><<<pg, 64, 0, st>>>(d, n, 40, nblocks, pout); }, reps, st);
+      const float p1 = timeit([&] { k_chase_probe<1><<<pg, 64, 0, st>>>(d, n, 40, nblocks, pout); }, reps, st);
+      printf("chase probe: chase_block with a count-only visit %.4f ms, plain one-header chain %.4f ms\n", p0, p1);
+    }
+    {  // per-workgroup wall-clock stamps (entry, chase end, sum end, end) of one launch, relative to the first entry
+      const uint64_t nwg = (nblocks + 63) / 64;
+      uint64_t* stp;
+      CK(hipMalloc(&stp, nwg * 32));
+      for (int rep = 0; rep < 3; ++rep) {
+        k_chase<32, WV><<<(uint32_t)nwg, WV * 64, 0, st>>>(d, n, 40, nblocks, s.fbase, s.rbase, s.bsum, s.frags, s.srec, s.frag_cap,
+                                                  s.lb, stp, s.misc, s.epoch, ctx->tabs.initc, s.chase_direct, 0ull,
+                                                  s.wstart, (uint32_t)cus * kCrcWaves, s.xbal, s.xbal_on);
+        ++s.epoch;
+        CK(hipStreamSynchronize(st));
+      }
+      std::vector<uint64_t> h4(nwg * 4);
+      CK(hipMemcpy(h4.data(), stp, nwg * 32, hipMemcpyDeviceToHost));
+      uint64_t t0 = ~0ull;
+      for (uint64_t w = 0; w < nwg; ++w) t0 = std::min(t0, h4[4 * w]);
+      std::vector<double> col[4];
+      for (uint64_t w = 0; w < nwg; ++w)
+        for (int k = 0; k < 4; ++k) col[k].push_back((h4[4 * w + k] - t0) / 100.0);
+      const char* nm[4] = {"entry", "chase end", "sum end", "end"};
+      for (int k = 0; k < 4; ++k) {
+        std::vector<double> c = col[k];
+        std::sort(c.begin(), c.end());
+        printf("  k_chase stamps %-9s us: min %.2f p10 %.2f p50 %.2f p90 %.2f max %.2f\n", nm[k], c[0], c[c.size() / 10],
+               c[c.size() / 2], c[c.size() * 9 / 10], c.back());
+      }
+      // entry by workgroup id (dispatch order), every 32nd
+      printf("  k_chase entry by wg (every 32nd):");
+      for (uint64_t w = 0; w < nwg; w += 32) printf(" %.2f", col[0][w]);
+      printf("\n  k_chase chase end by wg (every 32nd):");
+      for (uint64_t w = 0; w < nwg; w += 32) printf(" %.2f", col[1][w]);
+      printf("\n");
+      CK(hipFree(stp));
+    }
+    CK(hipMemset(&s.misc[7], 0, 24));
+    crun(k_chase<16, WV>);
+    uint64_t m3[3];
+    CK(hipMemcpy(m3, &s.misc[7], 24, hipMemcpyDeviceToHost));
+    const double wl = (double)((nblocks + 63) / 64) * (reps + 1);
+    printf("  k_chase phase cycles per workgroup (s_memtime): chase %.0f  sum %.0f  writes %.0f\n", m3[0] / wl,
+           m3[1] / wl, m3[2] / wl);
+  };
+  if (argc > 3 && std::string(argv[3]) == "chase") {  // only k_chase, with 2 and with 4 waves per workgroup
+    chase_report(std::integral_constant<int, 2>{});
+    chase_report(std::integral_constant<int, 4>{});
+    return 0;
+  }
   if (argc > 5 && std::string(argv[3]) == "seqk") {  // N back-to-back launches of one kernel, per-launch times
     // v: -1 plain HBM stream (k_stream), -2 the decode pipeline, otherwise the k_crc variant v (runv's list)
     const int nrep = atoi(argv[4]), v = atoi(argv[5]);
@@ -528,65 +597,7 @@ int main(int argc, char** argv) {
     int hz = 0;
     CK(hipDeviceGetAttribute(&hz, hipDeviceAttributeWallClockRate, 0));  // kHz
     printf("  stamps: first WG start -> finalize %.1f us (wall clock %d kHz)\n", (m[M_T_FIN] - m[M_T_CRC0]) * 1e3 / hz, hz);
-    auto crun = [&](auto kern) {
-      return timeit([&] {
-        kern<<<(uint32_t)((nblocks + 63) / 64), 64, 0, st>>>(d, n, 40, nblocks, s.fbase, s.rbase, s.bsum, s.frags,
-                                                              s.srec, s.frag_cap, s.lb, s.lbe, s.misc, s.epoch,
-                                                              ctx->tabs.initc, s.chase_direct, 0ull, s.wstart,
-                                                              (uint32_t)cus * kCrcWaves, s.xbal, s.xbal_on);
-        ++s.epoch;
-      }, reps, st);
-    };
-    printf("k_chase alone %.4f  no sum %.4f  no writes %.4f  chase only %.4f ms  hold 16: %.4f ms\n", crun(k_chase<0>),
-           crun(k_chase<1>), crun(k_chase<2>), crun(k_chase<3>), crun(k_chase<256>));
-    {
-      uint32_t* pout;
-      CK(hipMalloc(&pout, (nblocks + 64) * 4));
-      const uint32_t pg = (uint32_t)((nblocks + 63) / 64);
-      const float p0 = timeit([&] { k_chase_probe<0><<<pg, 64, 0, st>>>(d, n, 40, nblocks, pout); }, reps, st);
-      const float p1 = timeit([&] { k_chase_probe<1><<<pg, 64, 0, st>>>(d, n, 40, nblocks, pout); }, reps, st);
-      printf("chase probe: chase_block with a count-only visit %.4f ms, plain one-header chain %.4f ms\n", p0, p1);
-    }
-    {  // per-workgroup wall-clock stamps (entry, chase end, sum end, end) of one launch, relative to the first entry
-      const uint64_t nwg = (nblocks + 63) / 64;
-      uint64_t* stp;
-      CK(hipMalloc(&stp, nwg * 32));
-      for (int rep = 0; rep < 3; ++rep) {
-        k_chase<32><<<(uint32_t)nwg, 64, 0, st>>>(d, n, 40, nblocks, s.fbase, s.rbase, s.bsum, s.frags, s.srec, s.frag_cap,
-                                                  s.lb, stp, s.misc, s.epoch, ctx->tabs.initc, s.chase_direct, 0ull,
-                                                  s.wstart, (uint32_t)cus * kCrcWaves, s.xbal, s.xbal_on);
-        ++s.epoch;
-        CK(hipStreamSynchronize(st));
-      }
-      std::vector<uint64_t> h4(nwg * 4);
-      CK(hipMemcpy(h4.data(), stp, nwg * 32, hipMemcpyDeviceToHost));
-      uint64_t t0 = ~0ull;
-      for (uint64_t w = 0; w < nwg; ++w) t0 = std::min(t0, h4[4 * w]);
-      std::vector<double> col[4];
-      for (uint64_t w = 0; w < nwg; ++w)
-        for (int k = 0; k < 4; ++k) col[k].push_back((h4[4 * w + k] - t0) / 100.0);
-      const char* nm[4] = {"entry", "chase end", "sum end", "end"};
-      for (int k = 0; k < 4; ++k) {
-        std::vector<double> c = col[k];
-        std::sort(c.begin(), c.end());
-        printf("  k_chase stamps %-9s us: min %.2f p10 %.2f p50 %.2f p90 %.2f max %.2f\n", nm[k], c[0], c[c.size() / 10],
-               c[c.size() / 2], c[c.size() * 9 / 10], c.back());
-      }
-      // entry by workgroup id (dispatch order), every 32nd
-      printf("  k_chase entry by wg (every 32nd):");
-      for (uint64_t w = 0; w < nwg; w += 32) printf(" %.2f", col[0][w]);
-      printf("\n  k_chase chase end by wg (every 32nd):");
-      for (uint64_t w = 0; w < nwg; w += 32) printf(" %.2f", col[1][w]);
-      printf("\n");
-      CK(hipFree(stp));
-    }
-    CK(hipMemset(&s.misc[7], 0, 24));
-    crun(k_chase<16>);
-    uint64_t m3[3];
-    CK(hipMemcpy(m3, &s.misc[7], 24, hipMemcpyDeviceToHost));
-    const double wl = (double)((nblocks + 63) / 64) * (reps + 1);
-    printf("  k_chase phase cycles per workgroup (s_memtime): chase %.0f  sum %.0f  writes %.0f\n", m3[0] / wl,
-           m3[1] / wl, m3[2] / wl);
+    chase_report(std::integral_constant<int, kChaseWaves>{});
   }
   // verify still OK after variants (re-run the real pipeline)
   CK(bcw_decode_segment_async(ctx, d, &p, &t, dres));

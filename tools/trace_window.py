@@ -27,7 +27,7 @@ for name in ("k_chase", "k_crc"):
                             "all_avg_us": round(statistics.mean(d), 2)}
 starts = [int(r["Start_Timestamp"]) for r in rows if "bcw::k_chase<" in r["Kernel_Name"]]
 ends = [int(r["End_Timestamp"]) for r in rows if "bcw::k_crc<" in r["Kernel_Name"]]
-if len(starts) > a.skip + a.steps:
+if len(starts) >= a.skip + a.steps and len(ends) >= a.skip + a.steps:
     out["timed_span_us_per_step"] = round((ends[a.skip + a.steps - 1] - starts[a.skip]) / 1000 / a.steps, 2)
 json.dump(out, open(a.o, "w"), indent=1)
 print(json.dumps(out))
