@@ -80,6 +80,20 @@ class ReadParams(C.Structure):
                 ("etag_size", C.c_uint32), ("verify", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class GetParams(C.Structure):
+    _fields_ = [("ns_size", C.c_uint32), ("etag_size", C.c_uint32), ("verify", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class GetOut(C.Structure):
+    _fields_ = [("get_status", u8p), ("rd_status", u8p), ("fid", u64p), ("off", u64p), ("size", u64p),
+                ("pay_off", u64p), ("payload", u8p), ("payload_cap", C.c_uint64), ("table", RecordTable)]
+
+
+class GetResult(C.Structure):
+    _fields_ = [("n_found", C.c_uint64), ("n_ok", C.c_uint64), ("payload_need", C.c_uint64), ("fits", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
 class IndexResult(C.Structure):
     _fields_ = [("n_in", C.c_uint64), ("n_done", C.c_uint64), ("err_class", C.c_int32), ("_pad", C.c_int32)]
 
@@ -134,6 +148,7 @@ IDX_FOUND, IDX_NOT_FOUND, IDX_SOFT_DELETED = 0, 1, 2
 IDX_ERR_FULL = 6
 RECOVER_NOT_RUN, RECOVER_HINT, RECOVER_HINT_WAL, RECOVER_WAL = 0, 1, 2, 3
 RD_OK, RD_BEYOND, RD_CORRUPTED, RD_CRC, RD_SIZE, RD_TYPE, RD_INCOMPLETE, RD_PANIC = range(8)
+GET_OK, GET_NOT_FOUND, GET_SOFT_DELETED, GET_NO_WAL, GET_READ, GET_RECORD = range(6)
 
 
 def _load():
@@ -203,6 +218,15 @@ def _load():
                                              C.POINTER(RecordTable)]),
         "bcw_read_records": (C.c_int, [vp, vp, C.POINTER(ReadParams), C.c_uint64, u64p, u64p, vp, u8p,
                                        C.POINTER(RecordTable)]),
+        "bcw_walset_create": (C.c_int, [vp, C.POINTER(vp)]),
+        "bcw_walset_destroy": (C.c_int, [vp]),
+        "bcw_walset_put": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, C.c_uint64]),
+        "bcw_walset_upload": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, C.c_uint64]),
+        "bcw_walset_remove": (C.c_int, [vp, C.c_uint64]),
+        "bcw_walset_count": (C.c_uint64, [vp]),
+        "bcw_get_records_async": (C.c_int, [vp, vp, C.POINTER(GetParams), C.c_uint64, vp, vp, C.POINTER(GetOut), vp]),
+        "bcw_get_records": (C.c_int, [vp, vp, C.POINTER(GetParams), C.c_uint64, vp, u64p, C.POINTER(GetOut),
+                                      C.POINTER(GetResult)]),
         "bcw_stage_create": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
         "bcw_stage_destroy": (C.c_int, [vp]),
         "bcw_stage_read": (C.c_int, [vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, C.c_uint32]),

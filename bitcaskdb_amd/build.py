@@ -7,7 +7,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRCS = [os.path.join(HERE, "csrc", f) for f in ("bcw_api.cpp", "bcw_decode.hip", "bcw_encode.hip", "bcw_fanout.cpp", "bcw_index.hip", "bcw_io.cpp", "bcw_read.hip")]
+SRCS = [os.path.join(HERE, "csrc", f) for f in ("bcw_api.cpp", "bcw_decode.hip", "bcw_encode.hip", "bcw_fanout.cpp", "bcw_get.hip", "bcw_index.hip", "bcw_io.cpp", "bcw_read.hip")]
 OUT = os.path.join(HERE, "libbcw.so")
 ARCH = os.environ.get("BCW_OFFLOAD_ARCH", "gfx950")
 
@@ -31,7 +31,8 @@ def build(force: bool = False, verbose: bool = True, sanitize: bool = False) -> 
     """sanitize: an ASan/UBSan build of the host code (device code unchanged) as libbcw_asan.so, for
     tools/sanitize_cpu.sh"""
     out = os.path.join(HERE, "libbcw_asan.so") if sanitize else OUT
-    deps = SRCS + [os.path.join(HERE, "csrc", h) for h in ("bcw_internal.h", "bcw_parse.h")] + \
+    deps = SRCS + [os.path.join(HERE, "csrc", h) for h in ("bcw_internal.h", "bcw_parse.h", "bcw_read_body.h",
+                                                          "bcw_walset.h")] + \
         [os.path.join(ROOT, "include", "bcw.h")]
     if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps):
         return out

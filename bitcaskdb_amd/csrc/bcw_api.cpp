@@ -499,7 +499,8 @@ int bcw_decode_fragments_async(bcw_ctx* c, const bcw_frag_table* d_frags) {
 }
 
 static const char* kKernelNames[K_NUM] = {"k_chase", "k_crc", "(retired)", "k_enc_prep", "k_enc_scan", "k_events",
-                                          "k_write", "k_hint_layout", "k_events_hint"};
+                                          "k_write", "k_hint_layout", "k_events_hint", "k_get_lookup",
+                                          "k_get_scan", "k_get_read"};
 
 int bcw_ctx_reserve_fragments(bcw_ctx* c, uint64_t n) {
   if (!c || n >= 0xfffffff0ull) return BCW_E_INVAL;

@@ -1,0 +1,427 @@
+// bcw_get.hip -- batched Get by key (DBImpl.Get, db_impl.go:567-587): keys -> index -> record bytes without leaving
+// HBM. The resident WAL set (bcw_walset) is manifest.ToWalWithRef (getWalRef, db_impl.go:589-593): fid -> (device
+// image, seg_len, base_time) as a device array sorted by fid.
+//
+// A get is four stream-ordered launches:
+//   k_get_lookup   (bcw_index.hip) one lane per key: murmur3, probe, the fid in the set, ReadRecord's span check;
+//                  the request's payload slot size and each 256-key workgroup's slot sum
+//   k_get_scan     one workgroup: exclusive scan of the workgroup sums, payload_need, fits, n_found
+//   k_get_offsets  each 256-key workgroup scans its slot sizes from its base: pay_off, in request order (no atomic
+//                  allocation: the layout never depends on scheduling)
+//   k_get_read     one wave per request (waves stride over the requests): the body of k_read_records
+//                  (bcw_read_body.h) against the request's own image and base time, the copy in 16 B units
+// When the payload does not fit (fits == 0) k_get_read returns at once: nothing but the lookup columns is written.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "bcw_internal.h"
+#include "bcw_read_body.h"
+
+struct bcw_walset {
+  bcw_ctx* ctx = nullptr;
+  bcw::WalTable t;
+  bcw::WalEnt* d_ents = nullptr;  // the device copy of t.ents
+  uint64_t d_cap = 0;
+  uint64_t* d_blk = nullptr;      // [2 * blk_cap] per lookup workgroup: slot sums, then found counts
+  uint64_t blk_cap = 0;
+};
+
+namespace bcw {
+namespace get {
+
+constexpr int kScanThreads = 1024;
+constexpr int kWaves = 4;
+
+// wave-inclusive scan
+__device__ __forceinline__ uint64_t wave_incl(uint64_t v, uint32_t lane) {
+  uint64_t incl = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint64_t t = __shfl_up(incl, d, 64);
+    if (lane >= (uint32_t)d) incl += t;
+  }
+  return incl;
+}
+
+// exclusive scan of v over the workgroup's `waves` waves; *total: the workgroup's sum. s_w: `waves` LDS words. Ends
+// with a barrier, so s_w may be reused at once.
+__device__ __forceinline__ uint64_t block_excl(uint64_t v, uint64_t* s_w, uint32_t waves, uint64_t* total) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint64_t incl = wave_incl(v, lane);
+  if (lane == 63) s_w[wave] = incl;
+  __syncthreads();
+  uint64_t pre = 0, tot = 0;
+  for (uint32_t w = 0; w < waves; ++w) {
+    if (w < wave) pre += s_w[w];
+    tot += s_w[w];
+  }
+  __syncthreads();
+  *total = tot;
+  return pre + incl - v;
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_get_scan(uint64_t* __restrict__ bsum,
+                                                           const uint64_t* __restrict__ bfound, uint64_t nb,
+                                                           uint64_t payload_cap, bcw_get_result* __restrict__ res) {
+  __shared__ uint64_t s_w[kScanThreads / 64];
+  const uint32_t tid = threadIdx.x;
+  uint64_t carry = 0, found = 0;
+  for (uint64_t base = 0; base < nb; base += kScanThreads) {
+    const uint64_t i = base + tid;
+    const uint64_t v = i < nb ? bsum[i] : 0;
+    found += i < nb ? bfound[i] : 0;
+    uint64_t tot;
+    const uint64_t ex = block_excl(v, s_w, kScanThreads / 64, &tot);
+    if (i < nb) bsum[i] = carry + ex;
+    carry += tot;
+  }
+  uint64_t nfound;
+  (void)block_excl(found, s_w, kScanThreads / 64, &nfound);
+  if (tid == 0) {
+    bcw_get_result r{};
+    r.n_found = nfound;
+    r.n_ok = 0;  // k_get_read counts
+    r.payload_need = carry;
+    r.fits = carry <= payload_cap ? 1u : 0u;
+    *res = r;
+  }
+}
+
+__global__ __launch_bounds__(kGetLookupKeys) void k_get_offsets(uint64_t* __restrict__ pay_off, uint64_t n,
+                                                                const uint64_t* __restrict__ bsum) {
+  __shared__ uint64_t s_w[kGetLookupKeys / 64];
+  const uint64_t i = (uint64_t)blockIdx.x * kGetLookupKeys + threadIdx.x;
+  const uint64_t v = i < n ? pay_off[i] : 0;
+  uint64_t tot;
+  const uint64_t ex = block_excl(v, s_w, kGetLookupKeys / 64, &tot);
+  if (i < n) pay_off[i] = bsum[blockIdx.x] + ex;
+}
+
+struct ReadArgs {
+  const WalEnt* wals;
+  uint32_t n_wals;
+  bcw_get_params p;
+  uint64_t n;
+  bcw_get_out out;
+  bcw_get_result* res;
+  const uint32_t* pow2;   // [kPow2Ops][8][16] nibble images of A_{8 * 2^k}
+  const uint32_t* initc;  // A_{8L}(0xFFFFFFFF)
+};
+
+__global__ __launch_bounds__(64 * kWaves) void k_get_read(ReadArgs A) {
+  __shared__ uint32_t t0[256];
+  __shared__ uint32_t sp2[kPow2Ops * 128];
+  __shared__ uint64_t s_fo[kWaves][rd::kMaxF];
+  __shared__ uint32_t s_fl[kWaves][rd::kMaxF];
+  if (!A.res->fits) return;  // the whole grid: no payload byte, no table row
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  if (A.p.verify) rd::load_verify_tables(t0, sp2, A.pow2, tid, 64 * kWaves);
+  __syncthreads();
+  const bool tab = A.out.table.status != nullptr;
+  uint64_t n_ok = 0;
+  for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < A.n; r += (uint64_t)gridDim.x * kWaves) {
+    const uint64_t off = A.out.off[r], size = A.out.size[r];
+    uint32_t gs = A.out.get_status[r];
+    if (gs != BCW_GET_OK) {  // decided by the lookup
+      if (tab && lane == 0) rd::write_row(A.out.table, r, off, size, 0, rd::ReadRow{});
+      continue;
+    }
+    const uint64_t fid = A.out.fid[r];
+    uint32_t lo = 0, hi = A.n_wals;
+    while (lo < hi) {
+      const uint32_t m = (lo + hi) >> 1;
+      if (A.wals[m].fid < fid) lo = m + 1; else hi = m;
+    }
+    const WalEnt W = A.wals[lo < A.n_wals ? lo : 0];  // the lookup found fid in this same set
+    const rd::ReadEnv E{W.seg, W.seg_len, A.p.verify, t0, sp2, A.initc, s_fo[wave], s_fl[wave]};
+    uint32_t nf = 0;
+    // size <= seg_len and off in [40, seg_len] (k_get_lookup): WalRecordSize's loop is bounded by the image
+    const uint32_t st = rd::read_walk<true>(E, off, size, rd::wal_record_size(off, size),
+                                            A.out.payload + A.out.pay_off[r], lane, nf);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane != 0) continue;
+    rd::ReadRow R;
+    if (st == BCW_RD_OK) R = rd::read_parse(E, W.base_time, A.p.ns_size, A.p.etag_size, size, nf);
+    gs = st != BCW_RD_OK ? BCW_GET_READ : R.status != BCW_ST_OK ? BCW_GET_RECORD : BCW_GET_OK;
+    A.out.rd_status[r] = (uint8_t)st;
+    A.out.get_status[r] = (uint8_t)gs;
+    if (tab) rd::write_row(A.out.table, r, off, size, nf, R);
+    n_ok += gs == BCW_GET_OK ? 1 : 0;
+  }
+  if (lane == 0 && n_ok) atomicAdd(reinterpret_cast<unsigned long long*>(&A.res->n_ok), (unsigned long long)n_ok);
+}
+
+}  // namespace get
+}  // namespace bcw
+
+using namespace bcw;
+
+namespace {
+
+// the device copy of the set follows the host table, after the gets already queued
+int ws_publish(bcw_walset* ws) {
+  hipStream_t st = ws->ctx->cur;
+  const uint64_t n = ws->t.ents.size();
+  if (n > ws->d_cap) {
+    const uint64_t cap = std::max<uint64_t>(16, std::max(n, ws->d_cap * 2));
+    WalEnt* d = nullptr;
+    if (hipMalloc(&d, cap * sizeof(WalEnt)) != hipSuccess) return BCW_E_NOMEM;
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(ws->d_ents);
+    ws->d_ents = d;
+    ws->d_cap = cap;
+  }
+  if (n && hipMemcpyAsync(ws->d_ents, ws->t.ents.data(), n * sizeof(WalEnt), hipMemcpyHostToDevice, st) != hipSuccess)
+    return BCW_E_HIP;
+  // the host table may change again as soon as this returns
+  return hipStreamSynchronize(st) == hipSuccess ? BCW_OK : BCW_E_HIP;
+}
+
+// an image the set owned, once no queued get can read it
+void ws_free_image(bcw_walset* ws, void* img) {
+  if (!img) return;
+  (void)hipStreamSynchronize(ws->ctx->cur);
+  (void)hipFree(img);
+}
+
+int ws_put(bcw_walset* ws, const WalEnt& e, void* own) {
+  void* old = nullptr;
+  try {
+    old = ws->t.put(e, own);
+  } catch (const std::bad_alloc&) {
+    return BCW_E_NOMEM;
+  }
+  const int rc = ws_publish(ws);
+  ws_free_image(ws, old);
+  return rc;
+}
+
+bool table_ok(const bcw_record_table& t) {
+  return !t.status || (t.foff && t.size && t.expire && t.key_len && t.val_len && t.meta_len && t.hdr_size && t.flags &&
+                       t.etag_off);
+}
+
+}  // namespace
+
+extern "C" {
+
+int bcw_walset_create(bcw_ctx* c, bcw_walset** out) {
+  if (!c || !out) return BCW_E_INVAL;
+  *out = nullptr;
+  bcw_walset* ws = new (std::nothrow) bcw_walset();
+  if (!ws) return BCW_E_NOMEM;
+  ws->ctx = c;
+  *out = ws;
+  return BCW_OK;
+}
+
+int bcw_walset_destroy(bcw_walset* ws) {
+  if (!ws) return BCW_E_INVAL;
+  DeviceGuard dg(ws->ctx->device);
+  (void)hipStreamSynchronize(ws->ctx->cur);
+  for (void* img : ws->t.owned) (void)hipFree(img);
+  (void)hipFree(ws->d_ents);
+  (void)hipFree(ws->d_blk);
+  delete ws;
+  return BCW_OK;
+}
+
+int bcw_walset_put(bcw_walset* ws, uint64_t fid, const uint8_t* d_seg, uint64_t seg_len, uint64_t base_time) {
+  if (!ws || (seg_len && !d_seg)) return BCW_E_INVAL;
+  DeviceGuard dg(ws->ctx->device);
+  if (!dg.ok) return BCW_E_HIP;
+  return ws_put(ws, WalEnt{fid, d_seg, seg_len, base_time}, nullptr);
+}
+
+int bcw_walset_upload(bcw_walset* ws, uint64_t fid, const uint8_t* h_seg, uint64_t seg_len, uint64_t base_time) {
+  if (!ws || (seg_len && !h_seg)) return BCW_E_INVAL;
+  DeviceGuard dg(ws->ctx->device);
+  if (!dg.ok) return BCW_E_HIP;
+  void* img = nullptr;
+  if (hipMalloc(&img, std::max<uint64_t>(seg_len, 16)) != hipSuccess) return BCW_E_NOMEM;
+  if (seg_len && (hipMemcpyAsync(img, h_seg, seg_len, hipMemcpyHostToDevice, ws->ctx->cur) != hipSuccess ||
+                  hipStreamSynchronize(ws->ctx->cur) != hipSuccess)) {
+    (void)hipFree(img);
+    return BCW_E_HIP;
+  }
+  const int rc = ws_put(ws, WalEnt{fid, (const uint8_t*)img, seg_len, base_time}, img);
+  if (rc == BCW_E_NOMEM && !ws->t.has(fid)) (void)hipFree(img);  // the table did not take it
+  return rc;
+}
+
+int bcw_walset_remove(bcw_walset* ws, uint64_t fid) {
+  if (!ws) return BCW_E_INVAL;
+  DeviceGuard dg(ws->ctx->device);
+  if (!dg.ok) return BCW_E_HIP;
+  bool found = false;
+  void* old = ws->t.remove(fid, &found);
+  if (!found) return BCW_OK;
+  const int rc = ws_publish(ws);
+  ws_free_image(ws, old);
+  return rc;
+}
+
+uint64_t bcw_walset_count(bcw_walset* ws) { return ws ? ws->t.ents.size() : 0; }
+
+int bcw_get_records_async(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p, uint64_t n, const uint8_t* d_keys,
+                          const uint64_t* d_key_off, const bcw_get_out* d_out, bcw_get_result* d_result) {
+  if (!ix || !ws || !p || !d_out || !d_result || index_ctx(ix) != ws->ctx) return BCW_E_INVAL;
+  const bcw_get_out& o = *d_out;
+  if (n && (!d_key_off || !o.get_status || !o.rd_status || !o.fid || !o.off || !o.size || !o.pay_off))
+    return BCW_E_INVAL;
+  if ((o.payload_cap && !o.payload) || !table_ok(o.table)) return BCW_E_INVAL;
+  bcw_ctx* c = ws->ctx;
+  DeviceGuard dg(c->device);
+  if (!dg.ok) return BCW_E_HIP;
+  hipStream_t st = c->cur;
+  const uint64_t nb = (n + kGetLookupKeys - 1) / kGetLookupKeys;
+  if (nb > ws->blk_cap) {
+    const uint64_t cap = std::max<uint64_t>(1024, std::max(nb, ws->blk_cap * 2));
+    uint64_t* d = nullptr;
+    if (hipMalloc(&d, 2 * cap * sizeof(uint64_t)) != hipSuccess) return BCW_E_NOMEM;
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(ws->d_blk);
+    ws->d_blk = d;
+    ws->blk_cap = cap;
+  }
+  uint64_t* bsum = ws->d_blk;
+  uint64_t* bfound = ws->d_blk + ws->blk_cap;
+  Prof* prof = &c->prof;
+  hipEvent_t ev = nullptr;
+
+  GetLookup g{};
+  g.wals = ws->d_ents;
+  g.n_wals = (uint32_t)ws->t.ents.size();
+  g.n = n;
+  g.keys = d_keys;
+  g.koff = d_key_off;
+  g.out = o;
+  g.bsum = bsum;
+  g.bfound = bfound;
+  prof->begin(K_GET_LOOKUP, st, ev);
+  if (ix_launch_get_lookup(ix, g, st) != hipSuccess) return BCW_E_HIP;
+  prof->end(K_GET_LOOKUP, st, ev);
+
+  prof->begin(K_GET_SCAN, st, ev);
+  get::k_get_scan<<<1, get::kScanThreads, 0, st>>>(bsum, bfound, nb, o.payload_cap, d_result);
+  if (nb) get::k_get_offsets<<<(uint32_t)nb, kGetLookupKeys, 0, st>>>(o.pay_off, n, bsum);
+  prof->end(K_GET_SCAN, st, ev);
+  if (hipGetLastError() != hipSuccess) return BCW_E_HIP;
+  if (n == 0) return BCW_OK;
+
+  get::ReadArgs A{};
+  A.wals = ws->d_ents;
+  A.n_wals = g.n_wals;
+  A.p = *p;
+  A.n = n;
+  A.out = o;
+  A.res = d_result;
+  A.pow2 = c->tabs.pow2;
+  A.initc = c->tabs.initc;
+  const uint64_t want = (n + get::kWaves - 1) / get::kWaves;
+  // a few rounds of resident workgroups (4 per CU at the kernel's registers): the dispatcher evens out requests of
+  // unequal size, and the verify tables are filled a bounded number of times however large n is
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(want, (uint64_t)c->num_cus * 32);
+  prof->begin(K_GET_READ, st, ev);
+  get::k_get_read<<<grid, 64 * get::kWaves, 0, st>>>(A);
+  prof->end(K_GET_READ, st, ev);
+  return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
+}
+
+int bcw_get_records(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p, uint64_t n, const uint8_t* h_keys,
+                    const uint64_t* h_key_off, const bcw_get_out* h_out, bcw_get_result* h_result) {
+  if (!ix || !ws || !p || !h_out || !h_result || index_ctx(ix) != ws->ctx) return BCW_E_INVAL;
+  const bcw_get_out& h = *h_out;
+  if (n && (!h_key_off || !h.get_status || !h.rd_status || !h.fid || !h.off || !h.size || !h.pay_off))
+    return BCW_E_INVAL;
+  if ((h.payload_cap && !h.payload) || !table_ok(h.table)) return BCW_E_INVAL;
+  *h_result = bcw_get_result{};
+  h_result->fits = 1;
+  if (n == 0) return BCW_OK;
+  const uint64_t kb = h_key_off[n] - h_key_off[0];
+  if (kb && !h_keys) return BCW_E_INVAL;
+  for (uint64_t i = 0; i < n; ++i)
+    if (h_key_off[i + 1] < h_key_off[i]) return BCW_E_INVAL;
+  bcw_ctx* c = ws->ctx;
+  DeviceGuard dg(c->device);
+  if (!dg.ok) return BCW_E_HIP;
+  const bool tab = h.table.status != nullptr;
+  const uint64_t kbp = (kb + 15) & ~15ull, pcap = (h.payload_cap + 15) & ~15ull;
+  // keys | payload | key_off, fid, off, size, pay_off (8 B) | table (3 x 8 + 5 x 4 + 4 x 1 = 48 B per row) | the two
+  // status columns | result (aligned up to 16)
+  const uint64_t bytes = kbp + pcap + 8 * (n + 1) + 32 * n + (tab ? 48 * n : 0) + 2 * n + sizeof(bcw_get_result) + 64;
+  void* mem = nullptr;
+  if (hipMalloc(&mem, bytes) != hipSuccess) return BCW_E_NOMEM;
+  uint8_t* m = (uint8_t*)mem;
+  uint8_t* d_keys = m; m += kbp;
+  bcw_get_out d{};
+  d.payload = m; m += pcap;
+  d.payload_cap = h.payload_cap;
+  uint64_t* d_koff = (uint64_t*)m; m += 8 * (n + 1);
+  d.fid = (uint64_t*)m; m += 8 * n;
+  d.off = (uint64_t*)m; m += 8 * n;
+  d.size = (uint64_t*)m; m += 8 * n;
+  d.pay_off = (uint64_t*)m; m += 8 * n;
+  bcw_record_table& dt = d.table;
+  if (tab) {
+    dt.capacity = n;
+    dt.foff = (uint64_t*)m; m += 8 * n;
+    dt.size = (uint64_t*)m; m += 8 * n;
+    dt.expire = (uint64_t*)m; m += 8 * n;
+    dt.key_len = (uint32_t*)m; m += 4 * n;
+    dt.val_len = (uint32_t*)m; m += 4 * n;
+    dt.meta_len = (uint32_t*)m; m += 4 * n;
+    dt.first_frag = (uint32_t*)m; m += 4 * n;
+    dt.emit_frag = (uint32_t*)m; m += 4 * n;
+    dt.hdr_size = m; m += n;
+    dt.flags = m; m += n;
+    dt.etag_off = m; m += n;
+    dt.status = m; m += n;
+  }
+  d.get_status = m; m += n;
+  d.rd_status = m; m += n;
+  bcw_get_result* d_res = (bcw_get_result*)(((uintptr_t)m + 15) & ~(uintptr_t)15);
+  if ((uint8_t*)(d_res + 1) > (uint8_t*)mem + bytes) {  // the carve-up above must stay inside the allocation
+    (void)hipFree(mem);
+    return BCW_E_INVAL;
+  }
+  hipStream_t st = c->cur;
+  std::vector<uint64_t> koff(n + 1);
+  for (uint64_t i = 0; i <= n; ++i) koff[i] = h_key_off[i] - h_key_off[0];
+  auto down = [&](void* dst, const void* src, uint64_t b) {
+    return !dst || b == 0 || hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, st) == hipSuccess;
+  };
+  bool ok = (kb == 0 || hipMemcpyAsync(d_keys, h_keys + h_key_off[0], kb, hipMemcpyHostToDevice, st) == hipSuccess) &&
+            hipMemcpyAsync(d_koff, koff.data(), 8 * (n + 1), hipMemcpyHostToDevice, st) == hipSuccess;
+  int rc = ok ? bcw_get_records_async(ix, ws, p, n, d_keys, d_koff, &d, d_res) : BCW_E_HIP;
+  if (rc == BCW_OK) {
+    ok = down(h_result, d_res, sizeof(bcw_get_result)) && down(h.get_status, d.get_status, n) &&
+         down(h.rd_status, d.rd_status, n) && down(h.fid, d.fid, 8 * n) && down(h.off, d.off, 8 * n) &&
+         down(h.size, d.size, 8 * n) && down(h.pay_off, d.pay_off, 8 * n) && hipStreamSynchronize(st) == hipSuccess;
+    rc = !ok ? BCW_E_HIP : h_result->fits ? BCW_OK : BCW_E_CAPACITY;
+  }
+  if (rc == BCW_OK) {
+    ok = down(h.payload, d.payload, h_result->payload_need);
+    if (ok && tab) {
+      const uint64_t k = std::min(n, h.table.capacity);
+      const bcw_record_table& t = h.table;
+      ok = down(t.foff, dt.foff, 8 * k) && down(t.size, dt.size, 8 * k) && down(t.expire, dt.expire, 8 * k) &&
+           down(t.key_len, dt.key_len, 4 * k) && down(t.val_len, dt.val_len, 4 * k) &&
+           down(t.meta_len, dt.meta_len, 4 * k) && down(t.first_frag, dt.first_frag, 4 * k) &&
+           down(t.emit_frag, dt.emit_frag, 4 * k) && down(t.hdr_size, dt.hdr_size, k) && down(t.flags, dt.flags, k) &&
+           down(t.etag_off, dt.etag_off, k) && down(t.status, dt.status, k);
+    }
+    ok = ok && hipStreamSynchronize(st) == hipSuccess;
+    if (!ok) rc = BCW_E_HIP;
+  }
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(mem);
+  return rc;
+}
+
+}  // extern "C"

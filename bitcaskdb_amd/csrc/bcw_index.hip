@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "bcw_internal.h"
+#include "bcw_read_body.h"
 
 namespace bcw {
 namespace ix {
@@ -112,15 +113,6 @@ struct Murmur {
   }
 };
 
-__device__ __forceinline__ uint4 shift16(uint4 v0, uint4 v1, uint32_t sh) {
-  const bool s2 = (sh & 8u) != 0, s1 = (sh & 4u) != 0;
-  const uint32_t b0 = s2 ? v0.z : v0.x, b1 = s2 ? v0.w : v0.y, b2 = s2 ? v1.x : v0.z, b3 = s2 ? v1.y : v0.w,
-                 b4 = s2 ? v1.z : v1.x, b5 = s2 ? v1.w : v1.y;
-  const uint32_t c0 = s1 ? b1 : b0, c1 = s1 ? b2 : b1, c2 = s1 ? b3 : b2, c3 = s1 ? b4 : b3, c4 = s1 ? b5 : b4;
-  const uint32_t b = sh & 3u;
-  return make_uint4(__builtin_amdgcn_alignbyte(c1, c0, b), __builtin_amdgcn_alignbyte(c2, c1, b),
-                    __builtin_amdgcn_alignbyte(c3, c2, b), __builtin_amdgcn_alignbyte(c4, c3, b));
-}
 // 16 bytes of buf at signed offset a; bytes outside [0, n) read as 0
 __device__ __forceinline__ uint4 load16u(const uint8_t* __restrict__ buf, uint64_t n, int64_t a) {
   if (a >= 0 && (uint64_t)(a & ~15ll) + 32 <= n) {
@@ -534,6 +526,76 @@ __global__ __launch_bounds__(256) void k_ix_get(Src s, uint64_t n, const Slot* _
   status[i] = st;
 }
 
+// The lookup of a batched Get (DBImpl.Get, db_impl.go:567-577), one lane per flat key as k_ix_get: Index.Get, then
+// getWalRef -- the value's fid in the resident set, a binary search -- then ReadRecord's span check off +
+// WalRecordSize(off, size) > seg_len (wal.go:562-564). size comes out of the index and is not trusted: size > seg_len
+// or an off outside [40, seg_len] is BEYOND before WalRecordSize's loop (size / 32761 rounds) is entered. A request
+// that will be read takes a payload slot of size rounded up to 16 bytes; the slot sizes go to out.pay_off and their
+// sum per workgroup to bsum (bfound: keys found) for the scan that lays the slots out in request order.
+__global__ __launch_bounds__(kGetLookupKeys) void k_get_lookup(Src s, GetLookup g, const Slot* __restrict__ slots,
+                                                               uint64_t mask, const uint8_t* __restrict__ arena) {
+  __shared__ uint64_t s_sum[kGetLookupKeys / 64], s_found[kGetLookupKeys / 64];
+  const uint64_t i = (uint64_t)blockIdx.x * kGetLookupKeys + threadIdx.x;
+  uint64_t slot = 0, found = 0;
+  if (i < g.n) {
+    s.keys_len = s.koff[g.n];
+    const Key k = make_key(s, i);
+    const uint64_t h = key_hash(s, k);
+    const uint64_t j = find_slot(s, k, h, slots, mask, arena);
+    uint8_t gs = BCW_GET_NOT_FOUND, rs = BCW_RD_OK;
+    uint64_t f = 0, o = 0, z = 0;
+    if (j != ~0ull && slots[j].live) {
+      found = 1;
+      f = slots[j].fid;
+      o = slots[j].off;
+      z = slots[j].size;
+      if (o == 0) {
+        gs = BCW_GET_SOFT_DELETED;
+      } else {
+        uint32_t lo = 0, hi = g.n_wals;
+        while (lo < hi) {
+          const uint32_t m = (lo + hi) >> 1;
+          if (g.wals[m].fid < f) lo = m + 1; else hi = m;
+        }
+        if (lo >= g.n_wals || g.wals[lo].fid != f) {
+          gs = BCW_GET_NO_WAL;
+        } else {
+          const uint64_t len = g.wals[lo].seg_len;
+          bool beyond = z > len || o < BCW_SUPER_BLOCK_SIZE || o > len;
+          if (!beyond) beyond = o + rd::wal_record_size(o, z) > len;  // no wrap: both terms are O(seg_len)
+          if (beyond) {
+            gs = BCW_GET_READ;
+            rs = BCW_RD_BEYOND;
+          } else {
+            gs = BCW_GET_OK;  // so far: k_get_read decides
+            slot = (z + 15) & ~15ull;
+          }
+        }
+      }
+    }
+    g.out.get_status[i] = gs;
+    g.out.rd_status[i] = rs;
+    g.out.fid[i] = f;
+    g.out.off[i] = o;
+    g.out.size[i] = z;
+    g.out.pay_off[i] = slot;
+  }
+  uint64_t sum = slot, nf = found;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    sum += __shfl_xor(sum, d, 64);
+    nf += __shfl_xor(nf, d, 64);
+  }
+  if ((threadIdx.x & 63u) == 0) { s_sum[threadIdx.x >> 6] = sum; s_found[threadIdx.x >> 6] = nf; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t a = 0, b = 0;
+    for (int w = 0; w < kGetLookupKeys / 64; ++w) { a += s_sum[w]; b += s_found[w]; }
+    g.bsum[blockIdx.x] = a;
+    g.bfound[blockIdx.x] = b;
+  }
+}
+
 // compactOneWal's doFilter (compaction.go:329-348, without the user CompactionFilter) of every delivered
 // row of a decoded data WAL: keep = Get succeeds (not deleted / soft-deleted) and still points at
 // (src fid, foff - 7) (compaction.go:302); rows the iteration does not deliver get 0
@@ -834,6 +896,17 @@ struct bcw_index {
 
 namespace bcw {
 bcw_ctx* index_ctx(const bcw_index* ix) { return ix ? ix->ctx : nullptr; }
+
+hipError_t ix_launch_get_lookup(bcw_index* x, const GetLookup& g, hipStream_t st) {
+  if (g.n == 0) return hipSuccess;
+  Src s{};
+  s.kind = SRC_FLAT;
+  s.keys = g.keys;
+  s.koff = g.koff;  // keys_len: the kernel reads koff[n]
+  k_get_lookup<<<(uint32_t)((g.n + kGetLookupKeys - 1) / kGetLookupKeys), kGetLookupKeys, 0, st>>>(
+      s, g, x->slots, x->cap - 1, x->arena);
+  return hipGetLastError();
+}
 }  // namespace bcw
 
 namespace {

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "bcw.h"
+#include "bcw_walset.h"
 
 namespace bcw {
 
@@ -99,7 +100,7 @@ struct Scratch {
 // Optional per-kernel HIP-event timing (bcw_ctx_set_profiling): events recorded on the launch
 // stream around every kernel of the pipeline.
 enum KernelId { K_CHASE = 0, K_CRC, K_RETIRED, K_ENC_PREP, K_ENC_SCAN, K_ENC_EVENTS, K_ENC_WRITE, K_ENC_HINT_LAYOUT,
-                K_ENC_EVENTS_HINT, K_NUM };
+                K_ENC_EVENTS_HINT, K_GET_LOOKUP, K_GET_SCAN, K_GET_READ, K_NUM };
 struct Prof {
   uint32_t mask = 0;   // bit k: time kernel id k
   uint32_t every = 1;  // time every `every`-th launch of a selected kernel
@@ -209,6 +210,23 @@ constexpr int kIxCounters = 16;
 int ix_filter_on(bcw_index* x, bcw_ctx* c, const uint8_t* d_seg, const bcw_decode_params* p,
                  const bcw_record_table* d_table, const bcw_decode_result* d_result, uint64_t src_fid, uint8_t* d_keep,
                  uint64_t* d_cnt, bcw_index_result* d_out);
+
+// The lookup step of a batched Get (bcw_get.hip drives it; the kernel lives with the index, bcw_index.hip): one lane
+// per key. Writes get_status / rd_status / fid / off / size, the request's slot size into out.pay_off (the scan
+// turns the column into offsets), and per workgroup of kGetLookupKeys keys the sum of its slots (bsum) and its found
+// keys (bfound). The index's buffers are taken when the call is made, on the index's context.
+constexpr int kGetLookupKeys = 256;
+struct GetLookup {
+  const WalEnt* wals;  // device, ascending fid
+  uint32_t n_wals;
+  uint64_t n;
+  const uint8_t* keys;
+  const uint64_t* koff;
+  bcw_get_out out;
+  uint64_t* bsum;
+  uint64_t* bfound;
+};
+hipError_t ix_launch_get_lookup(bcw_index* x, const GetLookup& g, hipStream_t st);
 
 // Host-side table builders (bcw_api.cpp).
 void build_initc(uint32_t* initc);

@@ -17,59 +17,12 @@
 #include <vector>
 
 #include "bcw_internal.h"
-#include "bcw_parse.h"
+#include "bcw_read_body.h"
 
 namespace bcw {
 namespace rd {
 
 constexpr int kWaves = 4;
-constexpr int kMaxF = 64;  // fragments recorded for the header parse (the header lies in the first ones)
-
-__device__ __forceinline__ uint64_t wal_record_size(uint64_t offset, uint64_t size) {
-  // WalRecordSize (wal.go:61-86), uint64 arithmetic
-  uint64_t left = size, phy = 0;
-  offset -= 40;
-  while (left > 0) {
-    uint64_t leftover = kBlock - (offset % kBlock);
-    if (leftover < kHdr) {
-      phy += leftover;
-      offset += leftover;
-      leftover = kBlock;
-    }
-    const uint64_t frag = left < leftover - kHdr ? left : leftover - kHdr;
-    phy += kHdr + frag;
-    offset += kHdr + frag;
-    left -= frag;
-  }
-  return phy;
-}
-
-__device__ __forceinline__ uint32_t byte_at(const uint8_t* __restrict__ seg, uint64_t n, uint64_t a) {
-  return a < n ? seg[a] : 0u;
-}
-
-// the payload's bytes through the fragment list recorded in LDS
-struct FragReader {
-  const uint8_t* seg;
-  uint64_t seg_len;
-  const uint64_t* fo;  // segment offset of each fragment's data
-  const uint32_t* fl;  // its length
-  uint32_t nf;
-  __device__ __forceinline__ uint32_t operator()(uint64_t pos) const {
-    for (uint32_t f = 0; f < nf; ++f) {
-      if (pos < fl[f]) return byte_at(seg, seg_len, fo[f] + pos);
-      pos -= fl[f];
-    }
-    return 0;
-  }
-};
-
-__device__ __forceinline__ uint32_t apply_nib(const uint32_t* __restrict__ t, uint32_t x) {
-  uint32_t r = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r ^= t[i * 16 + ((x >> (4 * i)) & 15u)];
-  return r;
-}
 
 struct ReadArgs {
   const uint8_t* seg;
@@ -91,113 +44,29 @@ __global__ __launch_bounds__(64 * kWaves) void k_read_records(ReadArgs A) {
   __shared__ uint64_t s_fo[kWaves][kMaxF];
   __shared__ uint32_t s_fl[kWaves][kMaxF];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  for (uint32_t i = tid; i < 256; i += 64 * kWaves) {
-    uint32_t c = i;
-    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
-    t0[i] = c;
-  }
-  for (uint32_t i = tid; i < kPow2Ops * 128; i += 64 * kWaves) sp2[i] = A.pow2[i];
+  load_verify_tables(t0, sp2, A.pow2, tid, 64 * kWaves);
   __syncthreads();
   const uint64_t r = (uint64_t)blockIdx.x * kWaves + wave;
   if (r >= A.n) return;
-  const uint8_t* seg = A.seg;
+  const ReadEnv E{A.seg, A.p.seg_len, A.p.verify, t0, sp2, A.initc, s_fo[wave], s_fl[wave]};
   const uint64_t n = A.p.seg_len;
   const uint64_t off = A.off[r], size = A.size[r];
-  uint8_t* out = A.payload + A.pay_off[r];
   uint32_t st = BCW_RD_OK;
   const uint64_t rs = wal_record_size(off, size);
   uint32_t nf = 0;
-  if (off + rs > n || off + rs < off) {
+  if (off + rs > n || off + rs < off)
     st = BCW_RD_BEYOND;  // "read beyond file size" (wal.go:562-564)
-  } else {
-    // WalParseRecord(size, 0, [][]byte{buffer}, verify) with buffer = the file's [off, off + rs)
-    uint64_t bo = 0, got = 0;
-    for (;;) {
-      if (bo + kHdr > rs) { st = BCW_RD_PANIC; break; }  // header := blks[0][blkOff:blkOff+7] out of range
-      const uint64_t ha = off + bo;
-      const uint32_t crc = byte_at(seg, n, ha) | byte_at(seg, n, ha + 1) << 8 | byte_at(seg, n, ha + 2) << 16 |
-                           byte_at(seg, n, ha + 3) << 24;
-      const uint64_t len = byte_at(seg, n, ha + 4) | byte_at(seg, n, ha + 5) << 8;
-      const uint32_t type = byte_at(seg, n, ha + 6);
-      bo += kHdr;
-      if (len > rs - bo) { st = BCW_RD_CORRUPTED; break; }  // ErrWalCorruptedData
-      const uint64_t ds = off + bo;  // the fragment's data in the segment
-      bo += len;
-      if (nf < (uint32_t)kMaxF && lane == 0) { s_fo[wave][nf] = ds; s_fl[wave][nf] = (uint32_t)len; }
-      ++nf;
-      // copy what fits the payload slot (record = append(record, data...); a longer record is a size error)
-      const uint64_t cl = got < size ? (len < size - got ? len : size - got) : 0;
-      for (uint64_t b = (uint64_t)lane * 16; b < cl; b += 64 * 16) {
-        uint8_t tmp[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) tmp[k] = (uint8_t)byte_at(seg, n, ds + b + k);
-        const uint64_t m = cl - b < 16 ? cl - b : 16;
-        for (uint64_t k = 0; k < m; ++k) out[got + b + k] = tmp[k];
-      }
-      if (A.p.verify) {
-        // lane l: raw CRC-32C (init 0) of its chunk [l*c, min((l+1)*c, len)), shifted to the data end
-        const uint64_t c = (len + 63) / 64;
-        const uint64_t a0 = (uint64_t)lane * c, a1 = a0 + c < len ? a0 + c : len;
-        uint32_t x = 0;
-        for (uint64_t q = a0; q < a1; ++q) x = (x >> 8) ^ t0[(x ^ byte_at(seg, n, ds + q)) & 0xffu];
-        if (a0 < a1) {
-          uint64_t dsh = len - a1;  // zero bytes after the chunk
-          for (int k = 0; dsh; ++k, dsh >>= 1)
-            if (dsh & 1u) x = apply_nib(sp2 + k * 128, x);
-        } else {
-          x = 0;
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) x ^= (uint32_t)__shfl_xor((int)x, d, 64);
-        // the init contribution A_{8L}(~0): the table up to one block, beyond (crafted lengths) by shifts
-        uint32_t ic = A.initc[len <= kBlock ? len : kBlock];
-        for (uint64_t dsh = len > kBlock ? len - kBlock : 0, k = 0; dsh; ++k, dsh >>= 1)
-          if (dsh & 1u) ic = apply_nib(sp2 + k * 128, ic);
-        const uint32_t c32 = ~(x ^ ic);  // CRC-32C = ~crc_update(~0, data)
-        const uint32_t masked = ((c32 >> 15) | (c32 << 17)) + 0xa282ead8u;  // ComputeCRC32 (utils.go:24-29)
-        if (masked != crc) { st = BCW_RD_CRC; break; }
-      }
-      got += len;
-      if (type == BCW_RECORD_FULL || type == BCW_RECORD_LAST) {
-        if (got != size) st = BCW_RD_SIZE;  // ErrWalMismatchSize
-        break;
-      }
-      if (type != BCW_RECORD_FIRST && type != BCW_RECORD_MIDDLE) { st = BCW_RD_TYPE; break; }
-      if (rs - bo <= kHdr) { st = BCW_RD_INCOMPLETE; break; }  // leftover <= 7: the block loop ends
-    }
-  }
+  else
+    st = read_walk<false>(E, off, size, rs, A.payload + A.pay_off[r], lane, nf);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   if (lane != 0) return;
   A.rd_status[r] = (uint8_t)st;
   if (!A.tab.status) return;
-  bcw_decode_params dp{};
-  dp.seg_len = n;
-  dp.base_time = A.p.base_time;
-  dp.ns_size = A.p.ns_size;
-  dp.etag_size = A.p.etag_size;
-  dp.mode = BCW_MODE_RECORD;
-  uint8_t status = BCW_ST_OK, hdr = 0, flags = 0, etag_off = 0;
-  uint64_t kl = 0, vl = 0, ml = 0, expire = 0, x0 = 0, x1 = 0;
-  if (st == BCW_RD_OK) {
-    FragReader fr{seg, n, s_fo[wave], s_fl[wave], nf < (uint32_t)kMaxF ? nf : (uint32_t)kMaxF};
-    parse_record(dp, fr, size, status, hdr, flags, etag_off, kl, vl, ml, expire, x0, x1);
-  }
-  const bcw_record_table& t = A.tab;
-  if (r >= t.capacity) return;
-  t.foff[r] = off + kHdr;
-  t.size[r] = size;
-  t.expire[r] = expire;
-  t.key_len[r] = (uint32_t)kl;
-  t.val_len[r] = (uint32_t)vl;
-  t.meta_len[r] = (uint32_t)ml;
-  if (t.first_frag) t.first_frag[r] = 0;
-  if (t.emit_frag) t.emit_frag[r] = nf ? nf - 1 : 0;
-  t.hdr_size[r] = hdr;
-  t.flags[r] = flags;
-  t.etag_off[r] = etag_off;
-  t.status[r] = status;
+  ReadRow R;
+  if (st == BCW_RD_OK) R = read_parse(E, A.p.base_time, A.p.ns_size, A.p.etag_size, size, nf);
+  write_row(A.tab, r, off, size, nf, R);
 }
 
 }  // namespace rd

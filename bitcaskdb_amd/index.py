@@ -5,6 +5,7 @@ Names, argument meaning and error behaviour follow wenzhang-dev/bitcaskDB:
   murmur3_sum64                            IndexOperator.Hash                index.go:15-19
   recover_from_wals                        DBImpl.recoverFromWals / recoverFromWal  db_impl.go:268-314
   compact_one_wal_filtered                 compactOneWal with doFilter       compaction.go:294-348
+  Index.get_records / WalSet               DBImpl.Get / getWalRef            db_impl.go:567-593, 607-619
 The index lives in HBM (bcw_index); every operation goes through the C-ABI, there is no host fallback.
 """
 from __future__ import annotations
@@ -15,7 +16,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .wal import (Context, Wal, WalError, WalFile, _ENC_ERRORS, _frag_error, _src_error, default_context)
+from .wal import (Context, Decoded, ErrInvalidData, RefPanic, Wal, WalError, WalFile, _ENC_ERRORS, _RD_ERRORS,
+                  _frag_error, _record_of, _src_error, default_context, load_wal)
 
 
 class ErrKeyNotFound(WalError):
@@ -56,6 +58,80 @@ class IndexStats:
     limited: int = 0
     evicted: int = 0
     evicted_bytes: int = 0
+
+
+class WalSet:
+    """The WAL files of a database that are resident in HBM (bcw_walset): fid -> (device image, size, baseTime), the
+    device-side manifest.ToWalWithRef (getWalRef, db_impl.go:589-593). A fid that is not in the set means "the WAL
+    is gone". Bound to one Context; gets pair it with an Index of the same Context."""
+
+    def __init__(self, ctx: Context | None = None):
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        rc = L.lib.bcw_walset_create(self.ctx.handle, C.byref(h))
+        if rc != 0:
+            raise RuntimeError(f"bcw_walset_create: {L.lib.bcw_strerror(rc).decode()}")
+        self._h = h
+
+    @property
+    def handle(self):
+        return self._h
+
+    def add(self, wal_or_bytes, fid: int | None = None):
+        """make a WAL resident under `fid` (default: the Wal's own): the set uploads the image and owns the copy. A
+        Wal brings its baseTime; bytes are loaded as LoadWal does (the super block is validated). A fid already
+        present is replaced."""
+        wal = wal_or_bytes if isinstance(wal_or_bytes, Wal) else load_wal(wal_or_bytes, fid or 0)
+        seg = np.ascontiguousarray(wal.data, dtype=np.uint8)
+        rc = L.lib.bcw_walset_upload(self._h, wal.fid if fid is None else fid,
+                                     seg.ctypes.data_as(C.c_void_p) if seg.size else None, seg.size, wal.base_time)
+        if rc != 0:
+            raise RuntimeError(f"bcw_walset_upload: {L.lib.bcw_strerror(rc).decode()}")
+
+    def put_device(self, fid: int, d_seg: int, seg_len: int, base_time: int):
+        """an image already in HBM (device pointer), caller-owned: it must outlive its entry"""
+        rc = L.lib.bcw_walset_put(self._h, fid, C.c_void_p(d_seg), seg_len, base_time)
+        if rc != 0:
+            raise RuntimeError(f"bcw_walset_put: {L.lib.bcw_strerror(rc).decode()}")
+
+    def remove(self, fid: int):
+        rc = L.lib.bcw_walset_remove(self._h, fid)
+        if rc != 0:
+            raise RuntimeError(f"bcw_walset_remove: {L.lib.bcw_strerror(rc).decode()}")
+
+    def __len__(self) -> int:
+        return int(L.lib.bcw_walset_count(self._h)) if self._h else 0
+
+    def close(self):
+        if self._h:
+            if self.ctx.handle:  # as Index.close: a set that outlived its context must not touch it
+                L.lib.bcw_walset_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+@dataclass
+class GetBatch:
+    """the columns of one bcw_get_records call (bcw_get_out / bcw_get_result)"""
+    rc: int
+    result: L.GetResult
+    get_status: np.ndarray
+    rd_status: np.ndarray
+    fid: np.ndarray
+    off: np.ndarray
+    size: np.ndarray
+    pay_off: np.ndarray
+    payload: np.ndarray
+    table: dict
+
+    def record_bytes(self, i: int) -> bytes:
+        o = int(self.pay_off[i])
+        return bytes(self.payload[o:o + int(self.size[i])])
 
 
 class Index:
@@ -219,6 +295,74 @@ class Index:
             raise RuntimeError(f"bcw_index_export: {L.lib.bcw_strerror(rc).decode()}")
         kbytes = keys.tobytes()
         return {kbytes[int(koff[i]):int(koff[i + 1])]: (int(fid[i]), int(off[i]), int(size[i])) for i in range(cap)}
+
+    # ---- batched Get by key (DBImpl.Get, db_impl.go:567-587) ----
+    def get_batch(self, walset: "WalSet", keys, verify: bool = False, ns_size: int = 20, etag_size: int = 20,
+                  payload_cap: int | None = None, fill: int = 0) -> "GetBatch":
+        """bcw_get_records of merged keys against the resident WALs of `walset`: the raw columns (GetBatch). With
+        payload_cap None the call is retried once with the size the first one reports; with a given payload_cap it
+        is made once, and a payload that does not fit comes back with rc E_CAPACITY and fits == 0 (the payload
+        buffer, pre-filled with `fill`, is then untouched)."""
+        n = len(keys)
+        flat, koff = _pack(keys)
+        cap = payload_cap if payload_cap is not None else max(1 << 16, 1024 * n)
+        p = L.GetParams(ns_size, etag_size, 1 if verify else 0, 0)
+        while True:
+            m = max(n, 1)
+            gst, rst = np.zeros(m, np.uint8), np.zeros(m, np.uint8)
+            fid, off, size, pay_off = (np.zeros(m, np.uint64) for _ in range(4))
+            pay = np.full(max(cap, 1), fill, dtype=np.uint8)
+            cols = {name: np.zeros(m, dtype=dt) for name, dt in L.TABLE_COLUMNS}
+            tab = L.RecordTable(n, *[cols[name].ctypes.data_as(getattr(L, "u8p" if dt == "u1" else
+                                                                       ("u32p" if dt == "u4" else "u64p")))
+                                     for name, dt in L.TABLE_COLUMNS])
+            out = L.GetOut(gst.ctypes.data_as(L.u8p), rst.ctypes.data_as(L.u8p), fid.ctypes.data_as(L.u64p),
+                           off.ctypes.data_as(L.u64p), size.ctypes.data_as(L.u64p), pay_off.ctypes.data_as(L.u64p),
+                           pay.ctypes.data_as(L.u8p), cap, tab)
+            res = L.GetResult()
+            rc = L.lib.bcw_get_records(self._h, walset.handle, C.byref(p), n, flat.ctypes.data_as(C.c_void_p),
+                                       koff.ctypes.data_as(L.u64p), C.byref(out), C.byref(res))
+            if rc == L.E_CAPACITY and payload_cap is None and int(res.payload_need) > cap:
+                cap = int(res.payload_need)
+                payload_cap = cap  # one retry
+                continue
+            if rc not in (0, L.E_CAPACITY):
+                raise RuntimeError(f"bcw_get_records: {L.lib.bcw_strerror(rc).decode()}")
+            return GetBatch(rc, res, gst[:n], rst[:n], fid[:n], off[:n], size[:n], pay_off[:n], pay,
+                            {k: v[:n] for k, v in cols.items()})
+
+    def get_records(self, walset: "WalSet", keys, verify: bool = False, ns_size: int = 20, etag_size: int = 20):
+        """DBImpl.Get (db_impl.go:567-587) of many merged keys at once, on the device: Index.Get, getWalRef, then
+        Wal.ReadRecord + RecordFromBytes against the resident image of the value's fid. One item per key: a
+        wal.Record (built as wal.read_records builds it), or the error instance the reference returns for it (not
+        raised): ErrKeyNotFound (also when the value's WAL is not in the set, db_impl.go:574-577),
+        ErrKeySoftDeleted, or the ErrWal* / ErrInvalidData / RefPanic class of a failed read or parse. The
+        reference joins ErrKeyNotFound onto those read errors (errors.Join(err, ErrKeyNotFound),
+        db_impl.go:609-617); here the item is the specific error alone. Retries once when the payload buffer of
+        the first call is too small (BCW_E_CAPACITY)."""
+        b = self.get_batch(walset, keys, verify, ns_size, etag_size)
+        if b.rc != 0:
+            raise RuntimeError(f"bcw_get_records: {L.lib.bcw_strerror(b.rc).decode()}")
+        view = Decoded(result=L.DecodeResult(), table=b.table, seg=None, mode=L.MODE_RECORD, ns_size=ns_size,
+                       etag_size=etag_size)
+        out = []
+        for i in range(len(keys)):
+            g = int(b.get_status[i])
+            if g == L.GET_OK:
+                out.append(_record_of(view, i, b.record_bytes(i)))
+            elif g in (L.GET_NOT_FOUND, L.GET_NO_WAL):
+                out.append(ErrKeyNotFound())
+            elif g == L.GET_SOFT_DELETED:
+                out.append(ErrKeySoftDeleted())
+            elif g == L.GET_READ:
+                out.append(_RD_ERRORS[int(b.rd_status[i])]())
+            elif b.table["status"][i] == L.ST_INVALID:
+                out.append(ErrInvalidData())
+            elif b.table["status"][i] == L.ST_PANIC:
+                out.append(RefPanic("slice bounds out of range"))
+            else:
+                out.append(WalError("record length >= 2^32 is not supported by the device table"))
+        return out
 
     # ---- table-driven (device-resident) Put loops ----
     def recover_segment(self, data, mode: int, fid: int, start_off: int, base_time: int, ns_size: int,

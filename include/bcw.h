@@ -18,6 +18,11 @@
  *                                  + HintWriter.AppendRecord    hint.go:109-117 -> HintRecord.Encode hint.go:32-48
  *     (BCW_ENC_HINT)     replaces  NewHintByWal                 hint.go:123-161
  *                        callers   compaction.go:203-211 (via compactOneWal), db_impl.go:545
+ *   bcw_get_records*     replaces  DBImpl.Get                   db_impl.go:567-587
+ *                        i.e.      Index.Get                    index.go:81-98
+ *                        plus      getWalRef                    db_impl.go:589-593  (bcw_walset_*)
+ *                        plus      readRecord                   db_impl.go:607-619  (Wal.ReadRecord wal.go:556-573,
+ *                                                                                    RecordFromBytes record.go:140-239)
  *   bcw_synth_segment    host WAL writer: Wal.WriteRecord wal.go:490-553 over Record.Encode
  *                                  record.go:57-138 (synthetic segments of the benchmark configs)
  *
@@ -565,6 +570,88 @@ int bcw_read_records_async(bcw_ctx* ctx, const uint8_t* d_seg, const bcw_read_pa
 int bcw_read_records(bcw_ctx* ctx, const uint8_t* h_seg, const bcw_read_params* p, uint64_t n,
                      const uint64_t* h_off, const uint64_t* h_size, uint8_t* h_payload, uint8_t* h_rd_status,
                      const bcw_record_table* h_table);
+
+/* ---- batched Get by key (DBImpl.Get, db_impl.go:567-587) -------------------------------------------------
+ * keys -> index -> record bytes without leaving HBM: Index.Get (index.go:81-98), getWalRef (db_impl.go:589-593),
+ * then readRecord (db_impl.go:607-619) = Wal.ReadRecord (wal.go:556-573) + RecordFromBytes (record.go:140-239), each
+ * request against the WAL image its index value names.
+ *
+ * The resident WAL set is the device-side counterpart of manifest.ToWalWithRef(fid) (db_impl.go:589-593): fid ->
+ * (device image, seg_len, base_time), bound to one context, kept as a device array sorted by fid that the kernels
+ * binary-search. A fid that is not in the set means "the WAL is gone". Changes are ordered on the context's stream
+ * against earlier and later gets; one caller at a time uses a set, as for the index. */
+typedef struct bcw_walset bcw_walset;
+int bcw_walset_create(bcw_ctx* ctx, bcw_walset** out);
+int bcw_walset_destroy(bcw_walset* ws);
+/* d_seg (device, on the context's device) is caller-owned and must outlive its entry. A fid already present is
+ * replaced (an image the set owned is freed once the stream has drained). */
+int bcw_walset_put(bcw_walset* ws, uint64_t fid, const uint8_t* d_seg, uint64_t seg_len, uint64_t base_time);
+/* The set copies the host image to device memory it owns, and frees it on remove, replace or destroy. */
+int bcw_walset_upload(bcw_walset* ws, uint64_t fid, const uint8_t* h_seg, uint64_t seg_len, uint64_t base_time);
+/* BCW_OK whether or not the fid was present. */
+int bcw_walset_remove(bcw_walset* ws, uint64_t fid);
+/* number of resident WALs (0 for NULL) */
+uint64_t bcw_walset_count(bcw_walset* ws);
+
+/* get_status per request, in the order the reference decides them */
+#define BCW_GET_OK 0           /* Get returns value and meta */
+#define BCW_GET_NOT_FOUND 1    /* index.Get -> ErrKeyNotFound */
+#define BCW_GET_SOFT_DELETED 2 /* index.Get -> ErrKeySoftDeleted (index.go:93-95); fid / off / size still reported */
+#define BCW_GET_NO_WAL 3       /* getWalRef(fid) == nil -> ErrKeyNotFound (db_impl.go:574-577) */
+#define BCW_GET_READ 4         /* wal.ReadRecord failed, rd_status says how (db_impl.go:609-612) */
+#define BCW_GET_RECORD 5       /* RecordFromBytes rejected the bytes, the table's status says how (db_impl.go:614-617) */
+
+typedef struct bcw_get_params {
+  uint32_t ns_size;
+  uint32_t etag_size;
+  uint32_t verify; /* ReadOptions.VerifyChecksum */
+  uint32_t _pad;
+} bcw_get_params;
+
+/* Outputs, every array with n entries (the table with table.capacity rows; table.status == NULL: no table).
+ * fid / off / size: the index value (zeros when not found). rd_status: BCW_RD_*, BCW_RD_OK unless get_status is
+ * BCW_GET_READ. Request i's slot in `payload` starts at pay_off[i] and is size[i] rounded up to 16 bytes when the key
+ * was found with a resident WAL and the record's span lies inside that WAL, else 0 bytes; slots are in request order
+ * (pay_off is their exclusive prefix sum, so the layout does not depend on scheduling). The record's bytes are
+ * payload[pay_off[i], pay_off[i] + size[i]) and its value payload[pay_off[i] + hdr_size[i] + key_len[i] .. +
+ * val_len[i]): no second copy of the value is made. The table has the meaning of bcw_read_records_async's (row i:
+ * request i, foff = off + 7; RecordFromBytes' fields when the read succeeded, zeros otherwise).
+ * The index's size is not trusted: a request whose size exceeds its WAL's length, or whose off lies inside the super
+ * block (off < 40; the reference's WalRecordSize wraps there and reads whatever the header bytes frame), is
+ * BCW_GET_READ / BCW_RD_BEYOND without WalRecordSize's loop being walked. */
+typedef struct bcw_get_out {
+  uint8_t* get_status;
+  uint8_t* rd_status;
+  uint64_t* fid;
+  uint64_t* off;
+  uint64_t* size;
+  uint64_t* pay_off;
+  uint8_t* payload;
+  uint64_t payload_cap;
+  bcw_record_table table;
+} bcw_get_out;
+
+typedef struct bcw_get_result {
+  uint64_t n_found;      /* keys the index holds (soft-deleted ones included) */
+  uint64_t n_ok;         /* requests with BCW_GET_OK (0 when fits == 0) */
+  uint64_t payload_need; /* sum of the slots */
+  uint32_t fits;         /* 0: payload_need > payload_cap. No payload byte and no table row was written; fid, off,
+                            size and pay_off are valid, get_status / rd_status hold what the lookup decided (NOT_FOUND,
+                            SOFT_DELETED, NO_WAL, READ / BEYOND; BCW_GET_OK for the requests still to be read).
+                            Retry with payload_need. */
+  uint32_t _pad;
+} bcw_get_result;
+
+/* Async, device-resident: n merged keys ns || key (key i = d_keys[d_key_off[i], d_key_off[i+1]), d_keys 16-byte
+ * aligned as a HIP allocator returns it), outputs and d_result on the device. Launches on the context's stream, does
+ * not synchronise. ix and ws must have been created on the same context (BCW_E_INVAL otherwise). The index is not
+ * modified; a get sees every batch queued before it. */
+int bcw_get_records_async(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p, uint64_t n, const uint8_t* d_keys,
+                          const uint64_t* d_key_off, const bcw_get_out* d_out, bcw_get_result* d_result);
+/* Synchronous, host in / host out. Returns BCW_E_CAPACITY (result and the lookup columns filled, h_out->payload and
+ * the table untouched) when h_out->payload_cap < payload_need, as bcw_encode_segment does. */
+int bcw_get_records(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p, uint64_t n, const uint8_t* h_keys,
+                    const uint64_t* h_key_off, const bcw_get_out* h_out, bcw_get_result* h_result);
 
 /* ---- host I/O staging: WAL files <-> HBM through pinned slices ---------------------------------------
  * The reference reads a segment with PreadFull per 32 KiB block (utils.go:32-48, wal_iterator.go:55)

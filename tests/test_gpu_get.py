@@ -1,0 +1,359 @@
+"""GPU parity of the batched Get by key (bcw_get_records / bcw_walset, DBImpl.Get db_impl.go:567-587) against the
+oracle: O.Index.get (Index.Get), the fid's image when it is in the set (getWalRef), O.read_record on that image
+(Wal.ReadRecord + WalParseRecord) and O.record_parse (RecordFromBytes).
+
+The database: three WALs (fids 3, 7, 12, a baseTime each) of ~300 records of every shape plus values that cross one
+and two block boundaries, ~50 keys present in two consecutive files, a first record that leaves 3 bytes in its block
+(the next record starts after the padding: an index value pointing at the padding has it inside its span, the only
+way padding gets there -- the writer never pads inside a record), payloads RecordFromBytes rejects, deletes, soft
+deletes and Puts with tampered values."""
+from __future__ import annotations
+
+import ctypes as C
+import random
+
+import numpy as np
+import pytest
+
+import _devmem as D
+import _oracle as O
+import cases
+from bitcaskdb_amd import Context, Index, WalSet
+from bitcaskdb_amd import _lib as L
+from bitcaskdb_amd import index as IX
+from bitcaskdb_amd import wal as W
+
+pytestmark = pytest.mark.gpu
+NS, ETAG = 20, 20
+NSB = cases.sha1("ns")[:NS]
+FIDS = (3, 7, 12)
+BASES = {3: cases.BASE, 7: cases.BASE + 1000, 12: cases.BASE + 50000}
+REC_FIELDS = ("expire", "key_len", "val_len", "meta_len", "hdr_size", "flags", "etag_off", "status")
+BIG = (5000, 32761 - 60, 40000, 70000)
+CORRUPT_ID = 900 + 10 * 2 + 2  # the 40 000-byte value of fid 12
+
+
+def ukey(i: int) -> bytes:
+    return b"key-%06d" % i
+
+
+def shaped(i: int, base: int) -> bytes:
+    """the shapes of cases.case_records_mixed, against the WAL's own baseTime"""
+    etag = cases.sha1("etag")
+    k = i % 4
+    if k == 0:
+        return cases.rec(i, 11, etag=etag, expire=base + 60, tomb=True, meta=b"\x81\xa3foo\xa3bar", base=base)
+    if k == 1:
+        return cases.rec(i, 11, etag=etag, expire=base + 61, base=base)
+    if k == 2:
+        return cases.rec(i, 0, etag=etag, expire=base + 62, tomb=True, meta=b"\x81\xa3foo\xa3bar", base=base)
+    return cases.rec(i, 0, base=base)
+
+
+def filler(i: int, total: int) -> bytes:
+    """a valid record of exactly `total` payload bytes"""
+    v = total - len(cases.rec(i, 0))
+    for _ in range(4):
+        r = cases.rec(i, v)
+        if len(r) == total:
+            return r
+        v -= len(r) - total
+    raise AssertionError("no record of that size")
+
+
+class DB:
+    pass
+
+
+@pytest.fixture(scope="module")
+def db(ctx):
+    d = DB()
+    d.img, d.offs = {}, {}
+    d.ix, d.oix = Index(ctx, keys=1 << 12), O.Index()
+    for w, fid in enumerate(FIDS):
+        base = BASES[fid]
+        wr = O.Writer(base, base)
+        offs = {}
+        first = 800 + w
+        offs[first] = (wr.write(filler(first, 32768 - 7 - 3)), 32768 - 7 - 3)  # leaves 3 bytes: padding follows
+        for i in list(range(250 * w, 250 * w + 300)) + [900 + 10 * w + j for j in range(len(BIG))]:
+            p = cases.rec(i, BIG[i % 10], base=base) if i >= 900 else shaped(i, base)
+            offs[i] = (wr.write(p), len(p))
+        if fid == 3:  # payloads RecordFromBytes rejects, last: IterateRecord stops at them
+            junk = bytearray(cases.rec(0, 0))
+            junk[1 + NS] = 0  # etag and expire flagged present, beyond the data: the reference panics
+            offs["invalid"] = (wr.write(bytes(range(60))), 60)
+            offs["panic"] = (wr.write(bytes(junk)), len(junk))
+        d.img[fid], d.offs[fid] = wr.data(), offs
+        d.ix.recover_segment(d.img[fid], L.MODE_RECORD, fid, 40, base, NS, ETAG)
+        d.oix.put_segment(d.img[fid], 40, base, NS, ETAG, 0, fid)
+    assert d.offs[3][800][0] + 7 + 32758 + 3 == 40 + 32768 == d.offs[3][0][0]  # the padding is where it is meant
+    n3, n12 = len(d.img[3]), len(d.img[12])
+    o5, z5 = d.offs[3][5]
+    o9, z9 = d.offs[12][509]
+    ops = [(ukey(10), L.IDX_DELETE, 0, 0, 0), (ukey(260), L.IDX_DELETE, 0, 0, 0), (ukey(700), L.IDX_DELETE, 0, 0, 0),
+           (ukey(11), L.IDX_SOFT_DELETE, 0, 0, 0), (ukey(511), L.IDX_SOFT_DELETE, 0, 0, 0),
+           (ukey(20), L.IDX_PUT, 3, d.offs[3][20][0], d.offs[3][20][1] + 1),
+           (ukey(21), L.IDX_PUT, 3, d.offs[3][21][0], d.offs[3][21][1] - 1),
+           (ukey(22), L.IDX_PUT, 3, d.offs[3][22][0], 0),
+           (ukey(23), L.IDX_PUT, 3, o5 + 13, z5),                       # into the middle of a record
+           (ukey(24), L.IDX_PUT, 3, n3 - 5, 11),                        # near the end of the file
+           (ukey(25), L.IDX_PUT, 3, d.offs[3][25][0], n3 + 1),          # size = seg_len + 1
+           (ukey(26), L.IDX_PUT, 12, d.offs[12][922][0], d.offs[12][922][1] - 1),
+           (ukey(27), L.IDX_PUT, 12, d.offs[12][500][0] - 3, d.offs[12][500][1]),  # the padding inside the span
+           (ukey(28), L.IDX_PUT, 12, o9, z9),                           # another key's record: a plain read
+           (ukey(29), L.IDX_PUT, 12, n12 - 20, 70000),
+           (ukey(30), L.IDX_PUT, 5, 40, 11),                            # a fid that was never resident
+           (b"junk-a", L.IDX_PUT, 3, *d.offs[3]["invalid"]), (b"junk-b", L.IDX_PUT, 3, *d.offs[3]["panic"]),
+           (b"", L.IDX_PUT, 7, *d.offs[7][300])]                        # the empty user key
+    d.ix.apply([o[1] for o in ops], [NSB + o[0] for o in ops], [o[2] for o in ops], [o[3] for o in ops],
+               [o[4] for o in ops])
+    for k, op, f, o, z in ops:
+        d.oix.set(NSB, k, op, f, o, z)
+    d.ukeys = sorted({ukey(i) for offs in d.offs.values() for i in offs if isinstance(i, int)}
+                     | {o[0] for o in ops})
+    d.absent = [b"absent-%03d" % i for i in range(40)]
+    q = d.ukeys + d.absent + [ukey(7)] * 5
+    random.Random(11).shuffle(q)
+    d.query = q
+    d.ws = walset_of(ctx, d)
+    yield d
+    d.ws.close()
+    d.ix.close()
+
+
+def walset_of(ctx, d, img=None) -> WalSet:
+    ws = WalSet(ctx)
+    for fid in reversed(FIDS):  # any order: the set sorts
+        ws.add(W.Wal(np.frombuffer((img or d.img)[fid], dtype=np.uint8), fid, 40, BASES[fid]))
+    assert len(ws) == len(FIDS)
+    return ws
+
+
+def expected(d, keys, verify, resident=FIDS, img=None):
+    """the oracle's DBImpl.Get per key: (get_status, rd_status, fid, off, size, slot, payload, row)"""
+    img = img or d.img
+    out = []
+    for k in keys:
+        st, (f, o, z) = d.oix.get(NSB, k)
+        if st == 1:
+            out.append((L.GET_NOT_FOUND, 0, 0, 0, 0, 0, None, None))
+        elif st == 2:
+            out.append((L.GET_SOFT_DELETED, 0, f, o, z, 0, None, None))
+        elif f not in resident:
+            out.append((L.GET_NO_WAL, 0, f, o, z, 0, None, None))
+        else:
+            rst, pay = O.read_record(img[f], o, z, verify)
+            slot = 0 if rst == L.RD_BEYOND else (z + 15) & ~15
+            if rst != 0:
+                out.append((L.GET_READ, rst, f, o, z, slot, None, None))
+            else:
+                row = O.record_parse(pay, BASES[f], NS, ETAG)
+                out.append((L.GET_OK if row["status"] == 0 else L.GET_RECORD, 0, f, o, z, slot, pay, row))
+    return out
+
+
+def check(b, exp):
+    """every column of a GetBatch against the oracle's results"""
+    pos = 0
+    for i, (gs, rst, f, o, z, slot, pay, row) in enumerate(exp):
+        assert (int(b.get_status[i]), int(b.rd_status[i])) == (gs, rst), (i, b.get_status[i], b.rd_status[i], gs, rst)
+        assert (int(b.fid[i]), int(b.off[i]), int(b.size[i])) == (f, o, z), i
+        assert int(b.pay_off[i]) == pos and pos % 16 == 0, (i, int(b.pay_off[i]), pos)
+        if pay is not None:
+            assert b.record_bytes(i) == pay, i
+            assert int(b.table["status"][i]) == int(row["status"]), i
+        if gs == L.GET_OK:
+            for fld in REC_FIELDS:
+                assert int(b.table[fld][i]) == int(row[fld]), (i, fld, int(b.table[fld][i]), int(row[fld]))
+            assert int(b.table["foff"][i]) == o + 7 and int(b.table["size"][i]) == z
+            h, kl, vl = int(row["hdr_size"]), int(row["key_len"]), int(row["val_len"])
+            assert b.record_bytes(i)[h + kl:h + kl + vl] == pay[h + kl:h + kl + vl]
+        pos += slot
+    r = b.result
+    assert int(r.payload_need) == pos and r.fits == 1
+    assert int(r.n_ok) == sum(e[0] == L.GET_OK for e in exp)
+    assert int(r.n_found) == sum(e[0] != L.GET_NOT_FOUND for e in exp)
+
+
+@pytest.mark.parametrize("verify", [False, True])
+def test_get_parity(ctx, db, verify):
+    exp = expected(db, db.query, verify)
+    seen = {e[0] for e in exp}
+    assert {L.GET_OK, L.GET_NOT_FOUND, L.GET_SOFT_DELETED, L.GET_NO_WAL, L.GET_READ, L.GET_RECORD} <= seen
+    assert {L.RD_BEYOND, L.RD_SIZE, L.RD_PANIC} <= {e[1] for e in exp if e[0] == L.GET_READ}
+    assert {1, 2} <= {int(e[7]["status"]) for e in exp if e[0] == L.GET_RECORD}
+    # the later fid won for the keys two files hold, and each file's baseTime shows in its expires
+    k = db.query.index(ukey(253))
+    assert exp[k][2] == 7 and int(exp[k][7]["expire"]) == BASES[7] + 60 + 253 % 4
+    for n in (0, 1, 5, 257, len(db.query)):
+        b = db.ix.get_batch(db.ws, [NSB + k for k in db.query[:n]], verify, NS, ETAG)
+        assert b.rc == 0
+        check(b, exp[:n])
+
+
+def test_get_missing_wal(ctx, db):
+    keys = [NSB + k for k in db.query]
+    full = expected(db, db.query, True)
+    ws = walset_of(ctx, db)
+    ws.remove(7)
+    ws.remove(99)  # not present: BCW_OK
+    assert len(ws) == 2
+    exp = expected(db, db.query, True, resident=(3, 12))
+    turned = [i for i, (a, e) in enumerate(zip(full, exp)) if a != e]
+    assert turned and all(exp[i][0] == L.GET_NO_WAL and full[i][2] == 7 for i in turned)
+    assert len(turned) == sum(e[2] == 7 for e in full)
+    check(db.ix.get_batch(ws, keys, True, NS, ETAG), exp)
+    dev = D.upload(db.img[7])  # caller-owned image
+    ws.put_device(7, dev.ptr, len(db.img[7]), BASES[7])
+    check(db.ix.get_batch(ws, keys, True, NS, ETAG), full)
+    ws.close()
+    dev.free()
+
+
+def test_get_corruption(ctx, db):
+    o, z = db.offs[12][CORRUPT_ID]
+    bad = bytearray(db.img[12])
+    bad[o + 7 + 20000] ^= 0x20  # inside the 40 000-byte value (its first fragment)
+    img = dict(db.img)
+    img[12] = bytes(bad)
+    ws = walset_of(ctx, db, img)
+    keys = [ukey(CORRUPT_ID), ukey(CORRUPT_ID + 1), ukey(5)]
+    for verify in (True, False):
+        exp = expected(db, keys, verify, img=img)
+        assert (exp[0][0], exp[0][1]) == ((L.GET_READ, L.RD_CRC) if verify else (L.GET_OK, L.RD_OK))
+        b = db.ix.get_batch(ws, [NSB + k for k in keys], verify, NS, ETAG)
+        check(b, exp)
+        if not verify:
+            assert b.record_bytes(0) == O.read_record(img[12], o, z, False)[1] != O.read_record(db.img[12], o, z)[1]
+    ws.close()
+
+
+def test_get_capacity(ctx, db):
+    keys = [NSB + k for k in db.query]
+    exp = expected(db, db.query, False)
+    need = sum(e[5] for e in exp)
+    b = db.ix.get_batch(db.ws, keys, False, NS, ETAG, payload_cap=need - 1, fill=0xAB)
+    assert b.rc == L.E_CAPACITY and b.result.fits == 0 and int(b.result.payload_need) == need
+    assert (b.payload == 0xAB).all()
+    pos = 0
+    for i, e in enumerate(exp):  # the lookup columns
+        assert (int(b.fid[i]), int(b.off[i]), int(b.size[i]), int(b.pay_off[i])) == (e[2], e[3], e[4], pos), i
+        if e[0] in (L.GET_NOT_FOUND, L.GET_SOFT_DELETED, L.GET_NO_WAL) or e[1] == L.RD_BEYOND:
+            assert (int(b.get_status[i]), int(b.rd_status[i])) == (e[0], e[1]), i
+        pos += e[5]
+    assert (b.table["status"] == 0).all() and (b.table["foff"] == 0).all()  # no table row either
+    b = db.ix.get_batch(db.ws, keys, False, NS, ETAG, payload_cap=int(b.result.payload_need), fill=0xAB)
+    assert b.rc == 0
+    check(b, exp)
+    b = db.ix.get_batch(db.ws, keys, False, NS, ETAG)  # the retry inside get_batch
+    assert b.rc == 0 and int(b.result.payload_need) == need
+
+
+def test_get_leaves_index_untouched(ctx, db):
+    before = (db.ix.stats(), sorted(db.ix.export().items()))
+    db.ix.get_batch(db.ws, [NSB + k for k in db.query], True, NS, ETAG)
+    assert (db.ix.stats(), sorted(db.ix.export().items())) == before
+
+
+def test_get_after_growth(ctx, db):
+    """an index that grew several times since it was created: the get reads the buffers of its own launch"""
+    ix = Index(ctx, keys=16)
+    cap0 = ix.stats().slot_capacity
+    ids = list(range(250, 550))
+    for r in range(10):  # 3 000 keys, ten batches; the first 300 are fid 7's records
+        ks = [NSB + (ukey(i) if r == 0 else b"grow-%d-%d" % (r, i)) for i in ids]
+        ix.apply([L.IDX_PUT] * len(ks), ks, [7] * len(ks), [db.offs[7][i][0] for i in ids],
+                 [db.offs[7][i][1] for i in ids])
+    assert ix.stats().slot_capacity >= 4 * cap0 and ix.stats().live == 3000
+    keys = [NSB + (ukey(i) if r == 0 else b"grow-%d-%d" % (r, i)) for r in range(10) for i in ids]
+    b = ix.get_batch(db.ws, keys, True, NS, ETAG)
+    assert b.rc == 0 and int(b.result.n_found) == 3000 == int(b.result.n_ok)
+    for j in (0, 299, 300, 1234, 2999):
+        o, z = db.offs[7][ids[j % 300]]
+        assert (int(b.fid[j]), int(b.off[j]), int(b.size[j])) == (7, o, z)
+        assert b.record_bytes(j) == O.read_record(db.img[7], o, z)[1]
+    ix.close()
+
+
+def test_get_async_device_resident(ctx, db):
+    """device arrays in and out on the context's stream, one sync at the end: the sync call's answers"""
+    keys = [NSB + k for k in db.query]
+    n = len(keys)
+    ref = db.ix.get_batch(db.ws, keys, True, NS, ETAG)
+    flat, koff = IX._pack(keys)
+    d_keys, d_koff = D.upload(flat), D.upload(koff.view(np.uint8))
+    col = {name: D.DevBuf(n * w) for name, w in (("get_status", 1), ("rd_status", 1), ("fid", 8), ("off", 8),
+                                                 ("size", 8), ("pay_off", 8))}
+    cap = int(ref.result.payload_need)
+    d_pay, d_res, tab = D.DevBuf(cap, fill=0xAB), D.DevBuf(C.sizeof(L.GetResult)), D.DevTable(n)
+    out = L.GetOut(C.cast(col["get_status"].vp(), L.u8p), C.cast(col["rd_status"].vp(), L.u8p),
+                   C.cast(col["fid"].vp(), L.u64p), C.cast(col["off"].vp(), L.u64p), C.cast(col["size"].vp(), L.u64p),
+                   C.cast(col["pay_off"].vp(), L.u64p), C.cast(d_pay.vp(), L.u8p), cap, tab.t)
+    p = L.GetParams(NS, ETAG, 1, 0)
+    D.sync()
+    rc = L.lib.bcw_get_records_async(db.ix.handle, db.ws.handle, C.byref(p), n, d_keys.vp(), d_koff.vp(), C.byref(out),
+                                     d_res.vp())
+    assert rc == 0
+    ctx.sync()
+    res = L.GetResult.from_buffer_copy(d_res.download(C.sizeof(L.GetResult)).tobytes())
+    assert (res.n_found, res.n_ok, res.payload_need, res.fits) == (ref.result.n_found, ref.result.n_ok, cap, 1)
+    for name, w in (("get_status", 1), ("rd_status", 1), ("fid", 8), ("off", 8), ("size", 8), ("pay_off", 8)):
+        got = col[name].download(n * w).view(np.uint8 if w == 1 else np.uint64)
+        assert (got == getattr(ref, name)).all(), name
+    pay = d_pay.download(cap)
+    for i in range(n):
+        if ref.get_status[i] in (L.GET_OK, L.GET_RECORD):
+            o = int(ref.pay_off[i])
+            assert bytes(pay[o:o + int(ref.size[i])]) == ref.record_bytes(i), i
+    for name, _ in L.TABLE_COLUMNS:
+        if name not in ("aux0", "aux1"):
+            assert (tab.column(name, n) == ref.table[name]).all(), name
+    for b in [d_keys, d_koff, d_pay, d_res, *col.values()]:
+        b.free()
+
+
+def test_get_wrong_pairing(ctx, db):
+    other = Context(0)
+    ws = WalSet(other)
+    gst = np.zeros(1, np.uint8)
+    u = np.zeros(1, np.uint64)
+    out = L.GetOut(gst.ctypes.data_as(L.u8p), gst.ctypes.data_as(L.u8p), u.ctypes.data_as(L.u64p),
+                   u.ctypes.data_as(L.u64p), u.ctypes.data_as(L.u64p), u.ctypes.data_as(L.u64p), None, 0,
+                   L.RecordTable())
+    key, koff = np.frombuffer(NSB, dtype=np.uint8), np.array([0, NS], dtype=np.uint64)
+    p, res = L.GetParams(NS, ETAG, 0, 0), L.GetResult()
+    assert L.lib.bcw_get_records(db.ix.handle, ws.handle, C.byref(p), 1, key.ctypes.data_as(C.c_void_p),
+                                 koff.ctypes.data_as(L.u64p), C.byref(out), C.byref(res)) == L.E_INVAL
+    d_res = D.DevBuf(C.sizeof(L.GetResult))
+    assert L.lib.bcw_get_records_async(db.ix.handle, ws.handle, C.byref(p), 0, None, None, C.byref(out),
+                                       d_res.vp()) == L.E_INVAL
+    d_res.free()
+    ws.close()
+    other.close()
+
+
+def test_get_python_layer(ctx, db):
+    exp = expected(db, db.query, True)
+    got = db.ix.get_records(db.ws, [NSB + k for k in db.query], verify=True)
+    assert len(got) == len(exp)
+    rd_err = {L.RD_BEYOND: W.WalError, L.RD_CORRUPTED: W.ErrWalCorruptedData, L.RD_CRC: W.ErrWalMismatchCRC,
+              L.RD_SIZE: W.ErrWalMismatchSize, L.RD_TYPE: W.ErrWalUnknownRecordType,
+              L.RD_INCOMPLETE: W.ErrWalIncompleteRecord, L.RD_PANIC: W.RefPanic}
+    for k, g, (gs, rst, f, o, z, slot, pay, row) in zip(db.query, got, exp):
+        if gs == L.GET_OK:
+            h, kl, vl, ml = (int(row[c]) for c in ("hdr_size", "key_len", "val_len", "meta_len"))
+            assert isinstance(g, W.Record) and g.ns == pay[1:1 + NS] and g.key == pay[h:h + kl]
+            assert g.value == pay[h + kl:h + kl + vl]
+            assert g.meta.expire == int(row["expire"]) and g.meta.app_meta == pay[h + kl + vl:h + kl + vl + ml]
+            assert g.meta.flags == (1 if int(row["flags"]) & 4 else 0)
+            eo = int(row["etag_off"])
+            assert g.meta.etag == (b"" if int(row["flags"]) & 1 else pay[eo:eo + ETAG])
+        elif gs in (L.GET_NOT_FOUND, L.GET_NO_WAL):
+            assert type(g) is IX.ErrKeyNotFound, k
+        elif gs == L.GET_SOFT_DELETED:
+            assert type(g) is IX.ErrKeySoftDeleted, k
+        elif gs == L.GET_READ:
+            assert type(g) is rd_err[rst], (k, rst, g)
+        else:
+            assert type(g) is (W.ErrInvalidData if int(row["status"]) == 1 else W.RefPanic), k
