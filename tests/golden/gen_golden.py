@@ -33,6 +33,68 @@ def wal(payloads, create=BASE, base=BASE):
     return bytes(w.buf)
 
 
+def framed(items):
+    """hand-framed image: items are (type, data) fragments, laid out as the iterator walks them (7-byte header per
+    fragment, zero fill when fewer than 7 bytes are left in a block); a callable `data` is given the data bytes the
+    block still has room for and returns the fragment's data"""
+    buf = bytearray(P.super_block(BASE, BASE))
+    for typ, data in items:
+        left = 32768 - (len(buf) - 40) % 32768
+        if left < 7:
+            buf += bytes(left)
+            left = 32768
+        data = data(left - 7) if callable(data) else data
+        assert 7 + len(data) <= left, "a fragment never crosses a block"
+        buf += struct.pack("<IHB", P.compute_crc32(data), len(data), typ) + data
+    return bytes(buf)
+
+
+def irregular_shapes():
+    """fragment sequences WalIterator.Next accepts and the writer never writes (valid CRCs): First + Last in one
+    block, zero-length First / Middle / Last, Full after First, a lone Last, 96 one-byte fragments, a First that
+    leaves 3 bytes in its block, a Middle of 32761 bytes followed by one of 1 byte, a multi-block record with short
+    Middles, then ordinary Full records and one invalid row"""
+    meta = b"\x81\xa3foo\xa3bar"
+    items = []
+
+    def cut(p, cuts):
+        e = [0] + list(cuts) + [len(p)]
+        pieces = [p[a:b] for a, b in zip(e, e[1:])]
+        items.extend([(2, pieces[0])] + [(3, x) for x in pieces[1:-1]] + [(4, pieces[-1])])
+
+    def big(i, n, **kw):  # a compressible value keeps the committed file small
+        return P.record_encode(NS, b"test-key-%d" % i, bytes(k % 251 for k in range(n)), base_time=BASE, **kw)
+
+    cut(rec(0, 60, ETAG, BASE + 60), [30])
+    p = rec(1, 40, tomb=True, meta=meta)
+    cut(p, [0, 0, 25, 25, len(p)])
+    items += [(2, b"dangling-first"), (1, rec(2, 33, meta=b"\x80")), (4, rec(3, 0))]
+    cut(rec(4, 200, ETAG), range(1, 97))
+    # the rest of this block but 3 bytes, a whole block, one byte, the tail
+    p = big(5, 2 * 32768, expire=BASE + 61)
+    state = {}
+
+    def first_piece(room):
+        state["a"] = room - 3
+        return p[:room - 3]
+    items += [(2, first_piece), (3, lambda room: p[state["a"]:state["a"] + 32761]),
+              (3, lambda room: p[state["a"] + 32761:state["a"] + 32762]), (4, lambda room: p[state["a"] + 32762:])]
+    # multi-block with short Middles on both sides of the block end
+    q = big(6, 34000, etag=ETAG, tombstone=True, meta=meta)
+    st2 = {}
+
+    def upto_block_end(room):
+        st2["b"] = 300 + room
+        return q[300:300 + room]
+    items += [(2, q[:20]), (3, q[20:21]), (3, b""), (3, q[21:48]), (3, q[48:300]), (3, upto_block_end),
+              (3, lambda room: q[st2["b"]:st2["b"] + 1]), (3, lambda room: q[st2["b"] + 1:st2["b"] + 10]),
+              (4, lambda room: q[st2["b"] + 10:])]
+    items += [(1, rec(i, (0, 11, 300, 5000)[i % 4], ETAG if i % 2 else b"", BASE + 62 if i % 3 else 0)) for i in
+              range(7, 13)]
+    items.append((1, b"\x05garbage-bytes"))
+    return framed(items)
+
+
 def fixtures():
     out = {}
     # wal_iterator_test.go:11-40 and wal_test.go:17-70 scenarios
@@ -112,6 +174,7 @@ def fixtures():
     hb = bytearray(hw.buf)
     hb[40 + 7 + 20] = 0xF0  # corrupt a key length varint: CRC now fails
     out["hint_corrupt"] = (bytes(hb), {"mode": 1})
+    out["irregular_shapes"] = (irregular_shapes(), {})
     return out
 
 

@@ -11,6 +11,7 @@ import pytest
 
 import _oracle as O
 import cases
+from _encode_parity import run_compact, run_hint
 from bitcaskdb_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
@@ -44,36 +45,6 @@ def rec_of(rng, i, ns=20, etag_size=20, vlen=None, klen=None, kinds=True):
             meta = rng.choice([b"\x80", b"\xc0", b"\x81\xa0\xa0", b"\x82\xa0\xa0\xa0\xc0"])  # AppMetaSize 0
     nsb = bytes((65 + k) for k in range(ns))
     return O.record_encode(nsb, key, val, etag, expire, tomb, meta, BASE)
-
-
-def prefill(rng, w, nbytes):
-    while w.size() < nbytes:
-        w.write(bytes(rng.getrandbits(8) for _ in range(rng.randrange(5, 3000))))
-
-
-def run_compact(ctx, src, keep, ns=20, etag=20, dst_base=BASE, fid=9, pre_wal=0, pre_hint=0, seed=0):
-    rng = random.Random(seed)
-    dst, hint = O.Writer(dst_base, dst_base), O.Writer(dst_base, dst_base)
-    prefill(rng, dst, pre_wal)
-    prefill(rng, hint, pre_hint)
-    wal_pos, hint_pos = dst.size(), hint.size()
-    ec, er, nin, offs = O.compact_append(dst, hint, fid, src, 40, BASE, dst_base, ns, etag, keep)
-    res, wal, hb, goffs = ctx.encode(src, L.ENC_COMPACT, 40, dst_base, fid, wal_pos, hint_pos, ns, etag, keep)
-    assert res.err_class == ec, (res.err_class, ec, res.err_record, er)
-    if ec in (L.ENC_ERR_EXPIRE, L.ENC_ERR_PANIC) or (ec == L.ENC_ERR_SRC and er >= 0):
-        assert res.err_record == er
-    assert res.n_in == nin
-    ref_wal, ref_hint = dst.data()[wal_pos:], hint.data()[hint_pos:]
-    assert res.wal_end == dst.size() and res.hint_end == hint.size()
-    assert len(wal) == len(ref_wal)
-    if wal != ref_wal:
-        d = next(i for i in range(len(wal)) if wal[i] != ref_wal[i])
-        raise AssertionError(f"dst WAL differs at file offset {wal_pos + d} (appended byte {d} of {len(wal)})")
-    if hb != ref_hint:
-        d = next((i for i in range(min(len(hb), len(ref_hint))) if hb[i] != ref_hint[i]), min(len(hb), len(ref_hint)))
-        raise AssertionError(f"hint WAL differs at appended byte {d} ({len(hb)} vs {len(ref_hint)})")
-    np.testing.assert_array_equal(goffs[:nin], offs[:nin])
-    return res
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -170,14 +141,6 @@ def test_compact_errors(ctx):
     payloads[20] = b"\x05garbage-bytes"
     r = run_compact(ctx, make_src(payloads), np.ones(50, dtype=np.uint8))
     assert r.err_class == L.ENC_ERR_SRC and r.err_record == 20
-
-
-def run_hint(ctx, src, ns=20, etag=20, fid=5):
-    ec, er, nin, ref = O.hint_by_wal(src, fid, 40, BASE, ns, etag)
-    res, _, hb, _ = ctx.encode(src, L.ENC_HINT, 40, BASE, fid, 40, 40, ns, etag)
-    assert res.err_class == ec and res.n_in == nin
-    assert hb == ref[40:], "hint WAL bytes differ"
-    return res
 
 
 def test_hint_by_wal(ctx):

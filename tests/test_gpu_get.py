@@ -50,17 +50,6 @@ def shaped(i: int, base: int) -> bytes:
     return cases.rec(i, 0, base=base)
 
 
-def filler(i: int, total: int) -> bytes:
-    """a valid record of exactly `total` payload bytes"""
-    v = total - len(cases.rec(i, 0))
-    for _ in range(4):
-        r = cases.rec(i, v)
-        if len(r) == total:
-            return r
-        v -= len(r) - total
-    raise AssertionError("no record of that size")
-
-
 class DB:
     pass
 
@@ -75,7 +64,7 @@ def db(ctx):
         wr = O.Writer(base, base)
         offs = {}
         first = 800 + w
-        offs[first] = (wr.write(filler(first, 32768 - 7 - 3)), 32768 - 7 - 3)  # leaves 3 bytes: padding follows
+        offs[first] = (wr.write(cases.filler(first, 32768 - 7 - 3)), 32768 - 7 - 3)  # leaves 3 bytes: padding follows
         for i in list(range(250 * w, 250 * w + 300)) + [900 + 10 * w + j for j in range(len(BIG))]:
             p = cases.rec(i, BIG[i % 10], base=base) if i >= 900 else shaped(i, base)
             offs[i] = (wr.write(p), len(p))
@@ -357,3 +346,83 @@ def test_get_python_layer(ctx, db):
             assert type(g) is rd_err[rst], (k, rst, g)
         else:
             assert type(g) is (W.ErrInvalidData if int(row["status"]) == 1 else W.RefPanic), k
+
+
+def test_get_many_requests(ctx):
+    """a batch large enough that every loop of the get takes another pass: k_get_scan carries its running sum over
+    more than one chunk of 1024 workgroup sums (n > 262 144), k_get_read's waves stride over the requests
+    (n > 128 x CUs), and k_get_offsets meets 256-key workgroups whose slots are all zero, at the chunk edge too.
+    The oracle answers once per distinct key; every column is compared for every request."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = max(262144 + 256 + 3, 128 * cus + 777)
+    assert n > 1024 * 256 and n > 128 * cus
+    d = DB()
+    d.img, d.oix = {}, O.Index()
+    ix = Index(ctx, keys=1 << 12)
+    offs = {}
+    for fid in (3, 7):
+        wr = O.Writer(BASES[fid], BASES[fid])
+        for i in range(1000 * fid, 1000 * fid + 1000):
+            p = cases.rec(i, i % 53, base=BASES[fid])  # payloads of 35..87 bytes
+            offs[i] = (fid, wr.write(p), len(p))
+        d.img[fid] = wr.data()
+        ix.recover_segment(d.img[fid], L.MODE_RECORD, fid, 40, BASES[fid], NS, ETAG)
+        d.oix.put_segment(d.img[fid], 40, BASES[fid], NS, ETAG, 0, fid)
+    ops = [(ukey(3000 + i), L.IDX_DELETE, 0, 0, 0) for i in range(20)]
+    ops += [(ukey(3100 + i), L.IDX_SOFT_DELETE, 0, 0, 0) for i in range(20)]
+    ops += [(ukey(3200 + i), L.IDX_PUT, 5, offs[3200 + i][1], offs[3200 + i][2]) for i in range(20)]      # no WAL
+    ops += [(ukey(3300 + i), L.IDX_PUT, 3, len(d.img[3]) + 1 + i, offs[3300 + i][2]) for i in range(20)]  # BEYOND
+    ops += [(ukey(7000 + i), L.IDX_PUT, 7, offs[7000 + i][1], offs[7000 + i][2] + (1 if i % 2 else -1))
+            for i in range(20)]                                                                          # SIZE
+    ix.apply([o[1] for o in ops], [NSB + o[0] for o in ops], [o[2] for o in ops], [o[3] for o in ops],
+             [o[4] for o in ops])
+    for k, op, f, o, z in ops:
+        d.oix.set(NSB, k, op, f, o, z)
+    ukeys = [ukey(i) for i in offs] + [b"absent-%03d" % i for i in range(40)]
+    ws = WalSet(ctx)
+    for fid in (3, 7):
+        ws.add(W.Wal(np.frombuffer(d.img[fid], dtype=np.uint8), fid, 40, BASES[fid]))
+    nb = (n + 255) // 256
+    rng = np.random.default_rng(5)
+    try:
+        for verify in (True, False):
+            exp = expected(d, ukeys, verify, resident=(3, 7))
+            assert {L.GET_OK, L.GET_NOT_FOUND, L.GET_SOFT_DELETED, L.GET_NO_WAL, L.GET_READ} <= {e[0] for e in exp}
+            assert {L.RD_BEYOND, L.RD_SIZE} <= {e[1] for e in exp if e[0] == L.GET_READ}
+            col = {c: np.array([e[j] for e in exp], dtype=np.uint64) for j, c in
+                   enumerate(("get_status", "rd_status", "fid", "off", "size", "slot"))}
+            zero = np.nonzero(col["slot"] == 0)[0]
+            assert len(zero) >= 100
+            pick = rng.integers(0, len(ukeys), n)
+            for b in (0, 7, 1023, 1024, nb - 2):  # workgroups whose slots are all zero, two at the scan's chunk edge
+                pick[256 * b:256 * b + 256] = rng.choice(zero, 256)
+            keys = [NSB + ukeys[i] for i in pick]
+            slot = col["slot"][pick]
+            pay_off = np.concatenate([[0], np.cumsum(slot)[:-1]]).astype(np.uint64)
+            need = int(slot.sum())
+            assert need > 0 and int(slot[256 * 1024:].sum()) > 0  # the second chunk's workgroups have bytes to place
+            g = ix.get_batch(ws, keys, verify, NS, ETAG, payload_cap=need, fill=0xAB)
+            assert g.rc == 0 and g.result.fits == 1 and int(g.result.payload_need) == need
+            for c in ("get_status", "rd_status", "fid", "off", "size"):
+                np.testing.assert_array_equal(getattr(g, c).astype(np.uint64), col[c][pick], err_msg=c)
+            np.testing.assert_array_equal(g.pay_off, pay_off, err_msg="pay_off")
+            gs = col["get_status"][pick]
+            assert int(g.result.n_found) == int((gs != L.GET_NOT_FOUND).sum())
+            assert int(g.result.n_ok) == int((gs == L.GET_OK).sum())
+            ok = np.nonzero(gs == L.GET_OK)[0]
+            assert len(ok) > n // 2
+            np.testing.assert_array_equal(g.table["foff"][ok], g.off[ok] + 7)
+            np.testing.assert_array_equal(g.table["size"][ok], g.size[ok])
+            pay = g.payload.tobytes()
+            for r in ok.tolist():
+                o, want = int(pay_off[r]), exp[pick[r]][6]
+                assert pay[o:o + len(want)] == want, r
+        # one byte short of a slot: nothing but the lookup columns is written
+        g = ix.get_batch(ws, keys, False, NS, ETAG, payload_cap=need - 16, fill=0xAB)
+        assert g.rc == L.E_CAPACITY and g.result.fits == 0 and int(g.result.payload_need) == need
+        assert (g.payload == 0xAB).all()
+        np.testing.assert_array_equal(g.pay_off, pay_off)
+    finally:
+        ws.close()
+        ix.close()

@@ -120,3 +120,52 @@ def test_read_crafted_long_full_fragment(ctx, vlen):
     for img in (data, bytes(bad)):
         st = check(ctx, img, [40, 40, 40], [len(payload), len(payload) - 1, len(payload) + 1], verify=True)
         assert st[0] == (L.RD_OK if img is data else L.RD_CRC), st
+
+
+def test_read_more_than_64_fragments(ctx):
+    """a record of 71 fragments (a 2.3 MB value): more than the rd::kMaxF = 64 fragment slots a wave keeps in LDS,
+    through the batched read and through a Get, with and without checksum verification"""
+    from bitcaskdb_amd import Index, WalSet
+    big = cases.rec(50, vlen=2_310_000)
+    payloads = [cases.rec(i, vlen=30 + i) for i in range(20)] + [big] + [cases.rec(i, vlen=200) for i in range(21, 30)]
+    data, offs = cases.wal_of(payloads)
+    o, z = offs[20], len(big)
+    dec = O.decode(data, 40, BASE, 20, 20, want_bytes=False)
+    f0, f1 = int(dec.recs["first_frag"][20]), int(dec.recs["emit_frag"][20])
+    assert f1 - f0 + 1 == 71
+    fr66 = dec.frags[f0 + 66]
+    bad = bytearray(data)
+    bad[int(fr66["data_off"]) + int(fr66["len"]) // 2] ^= 0x08
+    bad = bytes(bad)
+    reqs_o = [o, offs[3], o, o, offs[25]]
+    reqs_z = [z, len(payloads[3]), z - 1, z + 1, len(payloads[25])]
+    for verify in (True, False):
+        st = check(ctx, data, reqs_o, reqs_z, verify)
+        # size + 1: the Last arrives one byte early (size mismatch). size - 1: WalRecordSize's span ends one byte
+        # inside the Last fragment, which WalParseRecord reports as corrupted data before it compares sizes
+        assert st.tolist() == [L.RD_OK, L.RD_OK, L.RD_CORRUPTED, L.RD_SIZE, L.RD_OK]
+        st = check(ctx, bad, reqs_o, reqs_z, verify)
+        assert st[0] == (L.RD_CRC if verify else L.RD_OK) and st[1] == L.RD_OK
+    pays, st, _ = ctx.read_records(bad, [o], [z], BASE, 20, 20, False)
+    assert st[0] == L.RD_OK and pays[0] != big and len(pays[0]) == z
+    # the same record through the Get
+    ns, key = big[1:21], big[big[0]:big[0] + 10]
+    ix = Index(ctx, keys=1 << 10)
+    ix.recover_segment(data, L.MODE_RECORD, 4, 40, BASE, 20, 20)
+    for img in (data, bad):
+        ws = WalSet(ctx)
+        ws.add(W.Wal(np.frombuffer(img, dtype=np.uint8), 4, 40, BASE))
+        for verify in (True, False):
+            g = ix.get_batch(ws, [ns + key, ns + b"key-%06d" % 3], verify, 20, 20)
+            rst, pay = O.read_record(img, o, z, verify)
+            assert rst == (L.RD_CRC if verify and img is bad else L.RD_OK)
+            assert (int(g.fid[0]), int(g.off[0]), int(g.size[0]), int(g.rd_status[0])) == (4, o, z, rst)
+            assert int(g.get_status[0]) == (L.GET_OK if rst == 0 else L.GET_READ) and int(g.get_status[1]) == L.GET_OK
+            if rst == 0:
+                assert g.record_bytes(0) == pay and (pay == big) == (img is data)
+                r = O.record_parse(pay, BASE, 20, 20)
+                for f in REC_FIELDS:
+                    assert int(g.table[f][0]) == int(r[f]), f
+            assert g.record_bytes(1) == payloads[3]
+        ws.close()
+    ix.close()
