@@ -3,7 +3,8 @@
 The product is libbcw.so (C-ABI in include/bcw.h, HIP kernels for gfx950 in csrc/). This package
 is the Python host mirror of the reference interface (wal.py: the WAL iterators, compaction re-encode,
 hint rebuild; index.py: the device-resident index, its rebuild from hint / data WALs, the device
-compaction filter and the batched Get by key against resident WALs) and its ctypes binding (_lib.py).
+compaction filter and the batched Get by key against resident WALs; write.py: the batched Write into the
+active WAL's resident image) and its ctypes binding (_lib.py).
 """
 from . import _lib
 from .wal import (Context, Decoded, ErrCorruptedHintRecord, ErrInvalidData, ErrShortFile, ErrWalMismatchBlockSize,
@@ -13,10 +14,12 @@ from .wal import (Context, Decoded, ErrCorruptedHintRecord, ErrInvalidData, ErrS
 from .staging import Stage
 from .index import (ErrKeyNotFound, ErrKeySoftDeleted, GetBatch, Index, WalSet, compact_one_wal_filtered, merged_key,
                     murmur3_sum64, recover_from_wals)
+from .write import ActiveWal, WriteBatch
 
 __all__ = ["Context", "Decoded", "ErrCorruptedHintRecord", "ErrInvalidData", "ErrShortFile",
            "ErrWalMismatchBlockSize", "ErrWalMismatchCRC", "ErrWalMismatchMagic", "ErrWalUnknownRecordType",
            "HintRecord", "Meta", "Record", "RefPanic", "Wal", "WalError", "compute_crc32", "default_context",
            "iterate_hint", "iterate_record", "load_wal", "_lib", "WalFile", "compact_one_wal",
            "new_hint_by_wal", "ErrKeyNotFound", "ErrKeySoftDeleted", "Index", "compact_one_wal_filtered",
-           "merged_key", "murmur3_sum64", "recover_from_wals", "Stage", "WalSet", "GetBatch"]
+           "merged_key", "murmur3_sum64", "recover_from_wals", "Stage", "WalSet", "GetBatch", "ActiveWal",
+           "WriteBatch"]

@@ -94,6 +94,29 @@ class GetResult(C.Structure):
                 ("_pad", C.c_uint32)]
 
 
+class WriteBatchArrays(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("keys", C.c_void_p), ("key_off", C.c_void_p), ("keys_len", C.c_uint64),
+                ("vals", C.c_void_p), ("val_off", C.c_void_p), ("vals_len", C.c_uint64), ("metas", C.c_void_p),
+                ("meta_off", C.c_void_p), ("metas_len", C.c_uint64), ("etags", C.c_void_p), ("expire", C.c_void_p),
+                ("flags", C.c_void_p)]
+
+
+class WriteParams(C.Structure):
+    _fields_ = [("fid", C.c_uint64), ("base_time", C.c_uint64), ("wal_pos", C.c_uint64), ("ns_size", C.c_uint32),
+                ("etag_size", C.c_uint32)]
+
+
+class WriteOut(C.Structure):
+    _fields_ = [("wal", C.c_void_p), ("wal_cap", C.c_uint64), ("rec_off", C.c_void_p), ("rec_size", C.c_void_p),
+                ("found", C.c_void_p), ("free_fid", C.c_void_p), ("free_bytes", C.c_void_p)]
+
+
+class WriteResult(C.Structure):
+    _fields_ = [("n_written", C.c_uint64), ("wal_end", C.c_uint64), ("wal_need", C.c_uint64),
+                ("err_record", C.c_int64), ("err_class", C.c_int32), ("idx_err", C.c_int32), ("fits", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
 class IndexResult(C.Structure):
     _fields_ = [("n_in", C.c_uint64), ("n_done", C.c_uint64), ("err_class", C.c_int32), ("_pad", C.c_int32)]
 
@@ -143,6 +166,8 @@ OPT_XCD_BALANCE = 6  # bcw_ctx_set_option: k_crc's stream split over the XCDs by
 E_IO = -6
 ENC_COMPACT, ENC_HINT = 0, 1
 ENC_ERR_NONE, ENC_ERR_SRC, ENC_ERR_EXPIRE, ENC_ERR_PANIC, ENC_ERR_TABLE, ENC_ERR_STALE = 0, 1, 2, 3, 4, 5
+ENC_ERR_BATCH = 6  # bcw_write_records*: a record the table cannot express
+WR_TOMBSTONE, WR_DELETED, WR_ETAG = 1, 2, 4
 IDX_PUT, IDX_DELETE, IDX_SOFT_DELETE = 0, 1, 2
 IDX_FOUND, IDX_NOT_FOUND, IDX_SOFT_DELETED = 0, 1, 2
 IDX_ERR_FULL = 6
@@ -227,6 +252,13 @@ def _load():
         "bcw_get_records_async": (C.c_int, [vp, vp, C.POINTER(GetParams), C.c_uint64, vp, vp, C.POINTER(GetOut), vp]),
         "bcw_get_records": (C.c_int, [vp, vp, C.POINTER(GetParams), C.c_uint64, vp, u64p, C.POINTER(GetOut),
                                       C.POINTER(GetResult)]),
+        "bcw_write_records_async": (C.c_int, [vp, C.POINTER(WriteParams), C.POINTER(WriteBatchArrays),
+                                              C.POINTER(WriteOut), vp]),
+        "bcw_write_records": (C.c_int, [vp, C.POINTER(WriteParams), C.POINTER(WriteBatchArrays), C.POINTER(WriteOut),
+                                        C.POINTER(WriteResult)]),
+        "bcw_record_encode": (C.c_int64, [vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp,
+                                          C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
+        "bcw_write_bound": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64]),
         "bcw_stage_create": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
         "bcw_stage_destroy": (C.c_int, [vp]),
         "bcw_stage_read": (C.c_int, [vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, C.c_uint32]),

@@ -362,6 +362,7 @@ int bcw_ctx_destroy(bcw_ctx* c) {
   if (c->cur) (void)hipStreamSynchronize(c->cur);
   free_scratch(c->s);
   free_enc_scratch(c->es);
+  put_scratch_free(c->ps);
   if (c->es.aux) (void)hipStreamSynchronize(c->es.aux);
   if (c->es.ev_scan) (void)hipEventDestroy(c->es.ev_scan);
   if (c->es.ev_hscan) (void)hipEventDestroy(c->es.ev_hscan);
@@ -500,7 +501,8 @@ int bcw_decode_fragments_async(bcw_ctx* c, const bcw_frag_table* d_frags) {
 
 static const char* kKernelNames[K_NUM] = {"k_chase", "k_crc", "(retired)", "k_enc_prep", "k_enc_scan", "k_events",
                                           "k_write", "k_hint_layout", "k_events_hint", "k_get_lookup",
-                                          "k_get_scan", "k_get_read"};
+                                          "k_get_scan", "k_get_read", "k_put_prep", "k_put_layout", "k_put_frags",
+                                          "k_put_write", "k_put_index"};
 
 int bcw_ctx_reserve_fragments(bcw_ctx* c, uint64_t n) {
   if (!c || n >= 0xfffffff0ull) return BCW_E_INVAL;
@@ -743,6 +745,8 @@ int bcw_encode_segment_async(bcw_ctx* c, const uint8_t* d_src, const bcw_encode_
 }  // extern "C"
 
 namespace bcw {
+int enc_scratch_reserve(bcw_ctx* c, uint64_t rows) { return ensure_enc_scratch(c, rows); }
+
 // Sync-API staging: the source segment into the context's device buffer, decoded into the context's
 // device table (grown until it holds every record), the fragment scratch retried until it fits.
 int sync_decode(bcw_ctx* c, const uint8_t* h_src, const bcw_decode_params& dp, bcw_decode_result& dres) {

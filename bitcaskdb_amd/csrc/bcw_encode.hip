@@ -61,6 +61,8 @@ enum {
   X_LAY = 8,      // per layout (wal: 8, hint: 16): +0 A_N, +1 nev, +2 k_end, +3 end, +4 b0, +5 U, +6 ok
 };
 constexpr int kLayStride = 8;
+static_assert(kXNin == X_NIN && kXErr == X_ERR && kXNDense == X_NDENSE && kXLay == X_LAY && kXPut >= X_LAY + 2 * kLayStride,
+              "emisc slots exported through bcw_internal.h");
 
 __device__ __forceinline__ uint32_t uvlen(uint64_t v) {
   uint32_t n = 1;
@@ -1854,6 +1856,41 @@ __global__ void k_enc_finalize(const uint64_t* __restrict__ emisc, uint32_t mode
 
 }  // namespace enc
 
+// the launches of one layout, shared by launch_encode and enc_layout_run: the 3-phase scan of the item sizes ...
+static void launch_scan(EncScratch& s, uint64_t rows, const uint32_t* sz, int over_rows, int lay, uint64_t* da,
+                        hipStream_t st) {
+  using namespace enc;
+  TileSum* tiles = static_cast<TileSum*>(s.tiles);
+  const uint32_t ntiles = (uint32_t)((rows + kTileItems - 1) / kTileItems) + 1;
+  k_tile_sums<<<ntiles, 256, 0, st>>>(sz, s.emisc, over_rows, tiles);
+  k_tile_scan<<<1, 1024, 0, st>>>(tiles, s.emisc, over_rows, lay, da);
+  k_tile_scatter<<<ntiles, 256, 0, st>>>(sz, s.emisc, over_rows, tiles, s.dsrc, da);
+}
+// ... and the event scan from file position pos
+static void launch_events(EncScratch& s, uint64_t rows, int lay, const uint64_t* da, uint64_t pos, hipStream_t st) {
+  using namespace enc;
+  Ev* evs = static_cast<Ev*>(s.ev);
+  const uint32_t nwin = (uint32_t)(rows / kEvWin + 1);
+  k_ev_win<<<nwin, 1024, 0, st>>>(da, s.emisc, lay, pos - 40, s.evt, s.hnl);
+  k_ev_walk<<<1, 64, 0, st>>>(s.emisc, lay, pos - 40, s.evt, s.evw, evs);
+  k_ev_emit<<<(nwin + 63) / 64, 64, 0, st>>>(da, s.emisc, s.evw, s.hnl, evs, s.evb);
+  k_ev_fix<<<1, 1024, 0, st>>>(da, s.emisc, lay, evs);
+}
+
+void enc_layout_reset(EncScratch& s, hipStream_t st) {
+  (void)hipMemsetAsync(s.emisc, 0, 64 * sizeof(uint64_t), st);
+  (void)hipMemsetAsync(s.emisc + enc::X_ERR, 0xff, sizeof(uint64_t), st);
+}
+
+hipError_t enc_layout_run(EncScratch& s, uint64_t rows, uint64_t wal_pos, hipStream_t st) {
+  using namespace enc;
+  launch_scan(s, rows, s.sz, 1, 0, s.da, st);
+  launch_events(s, rows, 0, s.da, wal_pos, st);
+  k_recoff<<<(uint32_t)((rows + 255) / 256) + 1, 256, 0, st>>>(s.da, s.dsrc, s.emisc, 0, static_cast<Ev*>(s.ev), s.evb,
+                                                               s.dpos, nullptr);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------
 hipError_t launch_encode(const EncLaunch& L, EncScratch& s, hipStream_t st, Prof* prof) {
   using namespace enc;
@@ -1876,18 +1913,13 @@ hipError_t launch_encode(const EncLaunch& L, EncScratch& s, hipStream_t st, Prof
   e.gen = L.gen;
   const uint64_t rows = L.rows;
   const bool compact = L.p.mode == BCW_ENC_COMPACT;
-  TileSum* tiles = static_cast<TileSum*>(s.tiles);
   Ev* evs = static_cast<Ev*>(s.ev);
-  (void)hipMemsetAsync(s.emisc, 0, 64 * sizeof(uint64_t), st);
-  (void)hipMemsetAsync(s.emisc + X_ERR, 0xff, sizeof(uint64_t), st);
+  enc_layout_reset(s, st);
   pr.begin(K_ENC_PREP, st, ev0);
   if (rows) k_enc_prep<<<(uint32_t)((rows + 255) / 256), 256, 0, st>>>(e, rows, s.sz, s.mflag, L.out.rec_off, s.emisc);
   pr.end(K_ENC_PREP, st, ev0);
-  const uint32_t ntiles = (uint32_t)((rows + kTileItems - 1) / kTileItems) + 1;
   auto scan = [&](const uint32_t* sz, int over_rows, int lay, uint64_t* da) {
-    k_tile_sums<<<ntiles, 256, 0, st>>>(sz, s.emisc, over_rows, tiles);
-    k_tile_scan<<<1, 1024, 0, st>>>(tiles, s.emisc, over_rows, lay, da);
-    k_tile_scatter<<<ntiles, 256, 0, st>>>(sz, s.emisc, over_rows, tiles, s.dsrc, da);
+    launch_scan(s, rows, sz, over_rows, lay, da, st);
   };
 
   WArgs W{};
@@ -1912,11 +1944,7 @@ hipError_t launch_encode(const EncLaunch& L, EncScratch& s, hipStream_t st, Prof
   auto layout = [&](int lay, const uint64_t* da, uint64_t pos) {
     const int kid = lay == 1 ? K_ENC_EVENTS_HINT : K_ENC_EVENTS;
     pr.begin(kid, st, ev0);
-    const uint32_t nwin = (uint32_t)(L.rows / kEvWin + 1);
-    k_ev_win<<<nwin, 1024, 0, st>>>(da, s.emisc, lay, pos - 40, s.evt, s.hnl);
-    k_ev_walk<<<1, 64, 0, st>>>(s.emisc, lay, pos - 40, s.evt, s.evw, evs);
-    k_ev_emit<<<(nwin + 63) / 64, 64, 0, st>>>(da, s.emisc, s.evw, s.hnl, evs, s.evb);
-    k_ev_fix<<<1, 1024, 0, st>>>(da, s.emisc, lay, evs);
+    launch_events(s, L.rows, lay, da, pos, st);
     pr.end(kid, st, ev0);
   };
   if (compact) {

@@ -51,7 +51,7 @@ struct Slot {
   uint64_t hash;  // murmur3 Sum64 of the merged key
   uint64_t fid, off, size;
   uint64_t live;  // 1: present (Put, SoftDelete); 0: absent (Delete)
-  uint64_t pad;
+  uint64_t pad;   // 0 between batches; inside a write batch the head of the key's op list (k_put_link)
 };
 static_assert(sizeof(Slot) == 64, "Slot layout");
 
@@ -65,7 +65,10 @@ enum { C_ARENA = 0, C_SLOTS = 1, C_LIVE = 2, C_OVERFLOW = 3, C_NIN = 4, C_DONE =
        C_EVICTED = 8, C_EVICTED_BYTES = 9, C_R_ARENA = 10, C_R_SLOTS = 11, C_R_FAIL = 12, C_NUM = 13 };
 
 // op sources
-enum { SRC_FLAT = 0, SRC_RECORD = 1, SRC_HINT = 2 };
+// SRC_BATCH: a write batch (bcw_write_records*): flat merged keys as SRC_FLAT, but the number of ops is read from a
+// device word (as the table kinds read cnt[C_NIN]), the op comes from the record's BCW_WR_* flags and the Put value
+// from the device rec_off / rec_size columns the writer produced
+enum { SRC_FLAT = 0, SRC_RECORD = 1, SRC_HINT = 2, SRC_BATCH = 3 };
 
 struct Src {
   int kind;
@@ -73,6 +76,13 @@ struct Src {
   const uint8_t* keys;
   const uint64_t* koff;
   uint64_t keys_len;
+  uint64_t kbias;  // added to every key offset (SRC_BATCH: `keys` is the array's address rounded down to 16 bytes)
+  // write batch
+  const uint64_t* b_nin;  // device word: ops to apply (0: the batch was rejected)
+  const uint64_t* b_off;
+  const uint64_t* b_size;
+  const uint8_t* b_flags;
+  uint64_t b_fid;
   // decoded table: the segment, its fragment table and record table
   const uint8_t* seg;
   uint64_t seg_len;
@@ -80,6 +90,8 @@ struct Src {
   bcw_record_table t;
   uint32_t start_off, ns;
 };
+
+__device__ __forceinline__ bool flat_keys(const Src& s) { return s.kind == SRC_FLAT || s.kind == SRC_BATCH; }
 
 __device__ __forceinline__ uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 __device__ __forceinline__ uint64_t fmix64(uint64_t k) {
@@ -168,8 +180,8 @@ __device__ uint8_t payload_byte(const Src& s, uint32_t f0, uint32_t f1, uint64_t
 __device__ __forceinline__ Key make_key(const Src& s, uint64_t i) {
   Key k{};
   k.ok = true;
-  if (s.kind == SRC_FLAT) {
-    const uint64_t a = s.koff[i], b = s.koff[i + 1];
+  if (flat_keys(s)) {
+    const uint64_t a = s.koff[i] + s.kbias, b = s.koff[i + 1] + s.kbias;
     k.la = (uint32_t)(b - a);
     k.lb = 0;
     k.a0 = (int64_t)a;
@@ -209,8 +221,8 @@ __device__ __forceinline__ uint4 key_chunk(const Src& s, const Key& k, uint32_t 
   const int32_t m0 = (int32_t)(16 * c);
   const int32_t L = (int32_t)k.len();
   uint4 v = make_uint4(0, 0, 0, 0);
-  const uint8_t* buf = s.kind == SRC_FLAT ? s.keys : s.seg;
-  const uint64_t n = s.kind == SRC_FLAT ? s.keys_len : s.seg_len;
+  const uint8_t* buf = flat_keys(s) ? s.keys : s.seg;
+  const uint64_t n = flat_keys(s) ? s.keys_len : s.seg_len;
   if (m0 < (int32_t)k.la) {  // part of A: merged [m0, min(la, m0 + 16))
     const int32_t hi = min((int32_t)k.la - m0, 16);
     if (k.ca) {
@@ -284,7 +296,10 @@ __global__ __launch_bounds__(256) void k_ix_keys(Src s, uint64_t n, const bcw_de
                                                  uint64_t* __restrict__ op_kref, uint64_t* __restrict__ op_hash) {
   const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
   uint64_t nin = n;
-  if (s.kind != SRC_FLAT) {
+  if (s.kind == SRC_BATCH) {
+    nin = *s.b_nin < n ? *s.b_nin : n;
+    if (i == 0) { cnt[C_NIN] = nin; cnt[C_FAIL] = 0; }
+  } else if (s.kind != SRC_FLAT) {
     const uint32_t fail = table_fail(R, gen, n);
     nin = fail ? 0 : delivered_rows(R);
     if (i == 0) { cnt[C_NIN] = nin; cnt[C_FAIL] = fail; }
@@ -452,6 +467,12 @@ __global__ __launch_bounds__(256) void k_ix_write(Src s, uint64_t n, uint64_t* _
         fid = v.fid[i];
         off = v.off[i];
         size = v.size[i];
+      } else if (s.kind == SRC_BATCH) {      // db_impl.go:441-448
+        const uint32_t fl = s.b_flags[i];
+        op = (fl & BCW_WR_DELETED) ? BCW_IDX_DELETE : (fl & BCW_WR_TOMBSTONE) ? BCW_IDX_SOFT_DELETE : BCW_IDX_PUT;
+        fid = s.b_fid;
+        off = s.b_off[i];
+        size = s.b_size[i];
       } else if (s.kind == SRC_RECORD) {
         fid = v.file_fid;                       // db_impl.go:307-313: Put(ns, key, wal.Fid(), foff - 7, size)
         off = s.t.foff[i] - kHdr;
@@ -477,6 +498,59 @@ __global__ __launch_bounds__(256) void k_ix_write(Src s, uint64_t n, uint64_t* _
   }
   (void)wave_alloc(&cnt[C_LIVE], (uint64_t)dlive);
   (void)wave_alloc(&cnt[C_DONE], done);
+}
+
+// ---- WriteStat of a write batch, composed on the device -----------------------------------------------
+// k_ix_claim reported, per op, the value the key held before the batch. An op preceded by another op on the same key
+// in this batch replaces that op's value instead (Put: the batch's fid and its size, SoftDelete: IndexValue{} with
+// fid 0 / size 0, Delete: nothing -- index.go:108-165; the host composition of bcw_index_apply_stat, here without a
+// round trip). The ops of one key are those of one slot: k_put_link chains them through the slot's spare word (an
+// unordered list: link[i] = the previous head), k_put_stat walks its key's list for the latest op before its own (the
+// list is as long as the key's ops in this batch), k_put_unlink clears the word again.
+__device__ __forceinline__ uint32_t batch_op(const Src& s, uint64_t i) {
+  const uint32_t fl = s.b_flags[i];
+  return (fl & BCW_WR_DELETED) ? BCW_IDX_DELETE : (fl & BCW_WR_TOMBSTONE) ? BCW_IDX_SOFT_DELETE : BCW_IDX_PUT;
+}
+__global__ __launch_bounds__(256) void k_put_link(const uint64_t* __restrict__ cnt, Slot* __restrict__ slots,
+                                                  const uint64_t* __restrict__ op_slot, uint64_t* __restrict__ link) {
+  const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
+  if (i >= cnt[C_NIN]) return;
+  const uint64_t sl = op_slot[i];
+  link[i] = sl == ~0ull ? 0 : atomicExch(reinterpret_cast<unsigned long long*>(&slots[sl].pad), (unsigned long long)(i + 1));
+}
+__global__ __launch_bounds__(256) void k_put_stat(Src s, const uint64_t* __restrict__ cnt, const Slot* __restrict__ slots,
+                                                  const uint64_t* __restrict__ op_slot, const uint64_t* __restrict__ link,
+                                                  uint8_t* __restrict__ found, uint64_t* __restrict__ free_fid,
+                                                  uint64_t* __restrict__ free_bytes) {
+  const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
+  if (i >= cnt[C_NIN]) return;
+  const uint64_t sl = op_slot[i];
+  uint64_t best = 0;  // 1 + the latest earlier op on this key
+  if (sl != ~0ull)
+    for (uint64_t p = slots[sl].pad; p != 0; p = link[p - 1])
+      if (p - 1 < i && p > best) best = p;
+  uint32_t f = found[i];
+  uint64_t ff = free_fid[i], fb = free_bytes[i];
+  if (best) {
+    const uint32_t op = batch_op(s, best - 1);
+    f = op != BCW_IDX_DELETE;
+    ff = op == BCW_IDX_PUT ? s.b_fid : 0;
+    fb = op == BCW_IDX_PUT ? s.b_size[best - 1] : 0;
+  }
+  if (!f) ff = fb = 0;
+  found[i] = (uint8_t)f;
+  free_fid[i] = ff;
+  free_bytes[i] = fb;
+}
+__global__ __launch_bounds__(256) void k_put_unlink(const uint64_t* __restrict__ cnt, Slot* __restrict__ slots,
+                                                    const uint64_t* __restrict__ op_slot) {
+  const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
+  if (i >= cnt[C_NIN]) return;
+  const uint64_t sl = op_slot[i];
+  if (sl != ~0ull) slots[sl].pad = 0;
+}
+__global__ void k_put_idx_err(const uint64_t* __restrict__ cnt, int32_t* __restrict__ idx_err) {
+  *idx_err = cnt[C_OVERFLOW] ? BCW_IDX_ERR_FULL : 0;
 }
 
 // ---- lookups -----------------------------------------------------------------------------------------
@@ -1091,6 +1165,37 @@ Src table_src(bcw_ctx* c, const uint8_t* d_seg, const bcw_decode_params* p, cons
 }  // namespace
 
 namespace bcw {
+int ix_put_batch(bcw_index* x, const PutIx& p) {
+  hipStream_t st = x->ctx->cur;
+  if (p.n) {
+    const int rc = ix_room(x, p.n, 31 * p.n + p.keys_len);
+    if (rc != BCW_OK) return rc;
+    Src s{};
+    s.kind = SRC_BATCH;
+    // every 16-byte granule a key load touches holds a byte of the keys array, whatever the array's alignment
+    s.kbias = (uint64_t)((uintptr_t)p.keys & 15u);
+    s.keys = p.keys - s.kbias;
+    s.koff = p.koff;
+    s.keys_len = p.keys_len + s.kbias;
+    s.b_nin = p.n_in;
+    s.b_off = p.rec_off;
+    s.b_size = p.rec_size;
+    s.b_flags = p.flags;
+    s.b_fid = p.fid;
+    const OpVals v{nullptr, nullptr, nullptr, nullptr, 0, 0};
+    ix_batch(x, s, p.n, nullptr, 0, v, p.found, p.free_fid, p.free_bytes);
+    if (p.found) {
+      const uint32_t grid = (uint32_t)((p.n + 255) / 256);
+      uint64_t* link = x->op_kref;  // free again once k_ix_claim has run
+      k_put_link<<<grid, 256, 0, st>>>(x->cnt, x->slots, x->op_slot, link);
+      k_put_stat<<<grid, 256, 0, st>>>(s, x->cnt, x->slots, x->op_slot, link, p.found, p.free_fid, p.free_bytes);
+      k_put_unlink<<<grid, 256, 0, st>>>(x->cnt, x->slots, x->op_slot);
+    }
+  }
+  if (p.idx_err) k_put_idx_err<<<1, 1, 0, st>>>(x->cnt, p.idx_err);
+  return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
+}
+
 int ix_export(bcw_index* x, const uint64_t* h_fids, uint64_t n_fids, IxSink& sink, uint64_t* n_out,
               uint64_t* key_bytes) {
   DeviceGuard dg(x->ctx->device);

@@ -100,7 +100,8 @@ struct Scratch {
 // Optional per-kernel HIP-event timing (bcw_ctx_set_profiling): events recorded on the launch
 // stream around every kernel of the pipeline.
 enum KernelId { K_CHASE = 0, K_CRC, K_RETIRED, K_ENC_PREP, K_ENC_SCAN, K_ENC_EVENTS, K_ENC_WRITE, K_ENC_HINT_LAYOUT,
-                K_ENC_EVENTS_HINT, K_GET_LOOKUP, K_GET_SCAN, K_GET_READ, K_NUM };
+                K_ENC_EVENTS_HINT, K_GET_LOOKUP, K_GET_SCAN, K_GET_READ, K_PUT_PREP, K_PUT_LAYOUT, K_PUT_FRAGS,
+                K_PUT_WRITE, K_PUT_INDEX, K_NUM };
 struct Prof {
   uint32_t mask = 0;   // bit k: time kernel id k
   uint32_t every = 1;  // time every `every`-th launch of a selected kernel
@@ -179,6 +180,16 @@ struct EncLaunch {
 };
 
 hipError_t launch_encode(const EncLaunch& L, EncScratch& s, hipStream_t stream, Prof* prof);
+// The writer's layout for a caller that filled s.sz itself (bcw_put.hip): enc_layout_reset clears the counters
+// (before the caller's own prep kernel, which sets emisc[kXNin] and min-reduces emisc[kXErr] as k_enc_prep does);
+// enc_layout_run is launch_encode's dst WAL layout -- the scan of s.sz over rows [0, first error), the event scan from
+// wal_pos and k_recoff -- and leaves s.da (y-coordinates), s.dpos (the offsets WriteRecord returns) and the layout's
+// counters emisc[kXLay + ...] (kXLayEnd: the file size after the append).
+constexpr int kXNin = 0, kXErr = 1, kXNDense = 3, kXLay = 8, kXLayEnd = kXLay + 3, kXPut = 32;
+void enc_layout_reset(EncScratch& s, hipStream_t stream);
+hipError_t enc_layout_run(EncScratch& s, uint64_t rows, uint64_t wal_pos, hipStream_t stream);
+// grow the context's encode scratch to `rows` records (bcw_api.cpp)
+int enc_scratch_reserve(bcw_ctx* c, uint64_t rows);
 size_t enc_sizeof_ev();
 size_t enc_sizeof_recdesc();
 size_t enc_sizeof_tile();
@@ -227,6 +238,38 @@ struct GetLookup {
   uint64_t* bfound;
 };
 hipError_t ix_launch_get_lookup(bcw_index* x, const GetLookup& g, hipStream_t st);
+
+// The index half of a batched Write (bcw_put.hip drives it; the kernels live with the index, bcw_index.hip): the ops
+// of a write batch through the index's batch launches. Keys are the batch's merged keys; the number of ops is read
+// from the device word *n_in (n, or 0 when the batch was rejected), off / size from the device rec_off / rec_size, the
+// op from the BCW_WR_* flags. found / free_fid / free_bytes (all or none): the WriteStat of every op, an earlier op of
+// the batch on the same key included. idx_err (device, may be NULL) receives 0 or BCW_IDX_ERR_FULL.
+struct PutIx {
+  uint64_t n;
+  const uint8_t* keys;
+  const uint64_t* koff;
+  uint64_t keys_len;
+  const uint64_t* n_in;
+  const uint64_t* rec_off;
+  const uint64_t* rec_size;
+  const uint8_t* flags;
+  uint64_t fid;
+  uint8_t* found;
+  uint64_t* free_fid;
+  uint64_t* free_bytes;
+  int32_t* idx_err;
+};
+int ix_put_batch(bcw_index* x, const PutIx& p);
+
+// Scratch of the batched Write (grow-only, per context; bcw_put.hip)
+struct PutScratch {
+  uint64_t rows_cap = 0, lit_cap = 0, frag_cap = 0;
+  uint8_t* lit = nullptr;    // [rows x stride] header literal per record (k_put_prep -> k_put_write)
+  uint32_t* hlen = nullptr;  // [rows] its length
+  void* frags = nullptr;     // [frag_cap] output fragments (k_put_frags -> k_put_write)
+  int write_resident = 0;    // k_put_write workgroups resident per CU (occupancy query on the context's device, once)
+};
+void put_scratch_free(PutScratch& s);
 
 // Host-side table builders (bcw_api.cpp).
 void build_initc(uint32_t* initc);
@@ -277,6 +320,7 @@ struct bcw_ctx {
   bcw::Tables tabs{};
   bcw::Scratch s{};
   bcw::EncScratch es{};
+  bcw::PutScratch ps{};
   // sync encode staging
   uint8_t* d_keep = nullptr;
   uint64_t d_keep_cap = 0;

@@ -1,0 +1,784 @@
+// bcw_put.hip -- MI355X (gfx950) kernels and entry points of the batched Write (DBImpl.Write, db_impl.go:343-431):
+// records that arrive as field arrays are encoded (Record.Encode, record.go:57-138), framed into the active WAL
+// (Wal.WriteRecord, wal.go:490-553) and applied to the device index (writeIndex, db_impl.go:434-454) without leaving
+// HBM. bcw_encode.hip re-encodes rows of a decoded WAL through that decode's fragment table; here the payload is
+// gathered from the caller's arrays.
+//
+// Pipeline (the index's context stream, no host synchronisation; DESIGN.md "Batched Write"):
+//   k_put_prep    per record: validation, the header literal (headerSize | ns | flags | 3 varints | etag | expire),
+//                 the payload size into EncScratch::sz, the first error as min (record << 2 | class)
+//   enc_layout_run  the writer's layout recurrence: bcw_encode.hip's scan, event scan and k_recoff, unchanged
+//   k_put_plan    one thread: the "accepted" word (no error and the bytes fit wal_cap) and bcw_write_result
+//   k_put_frags   per record: rec_off / rec_size and the record's output fragments (blk_end arithmetic) appended to
+//                 a fragment list
+//   k_put_write   one wave per output fragment: 16 B output units gathered from the header literal, key, value and
+//                 meta, stored, and folded into the fragment's CRC-32C; the record's first fragment zeroes the pad
+//                 before it
+//   ix_put_batch  the index ops (bcw_index.hip, SRC_BATCH) reading rec_off / rec_size and the accepted op count
+// Every store of k_put_frags / k_put_write and every index op is predicated on the accepted word: a rejected batch
+// leaves the output buffer, rec_off / rec_size and the index as they were (writeWal's ResetBuffer, db_impl.go:465-473).
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "bcw_internal.h"
+#include "bcw_read_body.h"
+
+namespace bcw {
+namespace put {
+
+constexpr uint32_t kL = kBlock;         // 32768
+constexpr uint32_t kM = kBlock - kHdr;  // 32761
+// emisc slots of the write (after the layouts' slots)
+enum { P_ACC = kXPut, P_NIN = kXPut + 1, P_NFRAG = kXPut + 2, P_FOVER = kXPut + 3 };
+// k_put_prep's error classes in the two low bits of emisc[kXErr]: BCW_ENC_ERR_EXPIRE (2) and BCW_ENC_ERR_PANIC (3) as
+// k_enc_prep packs them, and 1 for BCW_ENC_ERR_BATCH
+constexpr uint32_t kClsBatch = 1;
+
+struct PutDev {
+  uint64_t n;
+  const uint8_t *keys, *vals, *metas, *etags, *flags;
+  const uint64_t *koff, *voff, *moff, *expire;
+  uint64_t keys_len, vals_len, metas_len;
+  uint64_t base_time, wal_pos, wal_cap;
+  uint8_t* out;
+  uint64_t* rec_off;
+  uint64_t* rec_size;
+  uint32_t ns, etag, lstride;
+};
+
+// one output fragment (wal.go:519-546): header at file offset hp, flen payload bytes from payload offset x0
+struct PFrag {
+  uint64_t hp;
+  uint32_t rec, x0, flen, type;
+};
+static_assert(sizeof(PFrag) == 24, "PFrag layout");
+
+__device__ __forceinline__ uint32_t uvlen(uint64_t v) {
+  uint32_t n = 1;
+  while (v >= 0x80) { v >>= 7; ++n; }
+  return n;
+}
+__device__ __forceinline__ uint32_t uvput(uint8_t* p, uint64_t v) {
+  uint32_t n = 0;
+  while (v >= 0x80) { p[n++] = (uint8_t)(v | 0x80); v >>= 7; }
+  p[n++] = (uint8_t)v;
+  return n;
+}
+// first file offset past the block that holds P
+__device__ __forceinline__ uint64_t blk_end(uint64_t P) { return P + kL - (P - 40) % kL; }
+// file offset just past a record whose first header is at P, with a payload of len > 0 bytes
+__device__ __forceinline__ uint64_t rec_end(uint64_t P, uint64_t len) {
+  const uint64_t be = blk_end(P), ds = P + kHdr;
+  if (ds + len <= be) return ds + len;
+  const uint64_t rem = len - (be - ds);
+  const uint64_t q = (rem - 1) / kM;  // whole continuation blocks before the last fragment
+  return be + q * kL + kHdr + (rem - q * kM);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_put_prep: Record.Encode's header and size per record (record.go:57-138). The literal is headerSize (truncated
+// to a byte, record.go:109) | ns | flags | uvarint(len(key)) | uvarint(len(value)) | uvarint(len(meta)) | etag |
+// uvarint(expire - baseTime), at most 2 + ns + 15 + etag + 5 bytes, kept at lit + i * lstride for the writer.
+__global__ __launch_bounds__(256) void k_put_prep(PutDev d, uint32_t* __restrict__ sz, uint8_t* __restrict__ lit,
+                                                   uint32_t* __restrict__ hlen, uint64_t* __restrict__ emisc) {
+  const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
+  if (i == 0) emisc[kXNin] = d.n;
+  if (i >= d.n) return;
+  auto fail = [&](uint32_t cls) {
+    atomicMin((unsigned long long*)&emisc[kXErr], (unsigned long long)(i << 2 | cls));
+    sz[i] = 0;
+  };
+  const uint64_t k0 = d.koff[i], k1 = d.koff[i + 1], v0 = d.voff[i], v1 = d.voff[i + 1], m0 = d.moff[i],
+                 m1 = d.moff[i + 1];
+  // a record whose ranges do not lie inside the arrays is never read
+  if (k0 > k1 || k1 > d.keys_len || v0 > v1 || v1 > d.vals_len || m0 > m1 || m1 > d.metas_len) return fail(kClsBatch);
+  const uint64_t klm = k1 - k0, vl = v1 - v0, ml = m1 - m0;
+  const uint32_t fl = d.flags[i];
+  if (klm < d.ns || (klm | vl | ml) >> 32 || ((fl & BCW_WR_ETAG) && d.etag && !d.etags)) return fail(kClsBatch);
+  const uint64_t kl = klm - d.ns;
+  const uint32_t el = (fl & BCW_WR_ETAG) ? d.etag : 0u;
+  const uint64_t expire = d.expire[i];
+  uint32_t flag = (el == 0 ? 1u : 0u) | ((fl & BCW_WR_TOMBSTONE) ? 4u : 0u);
+  uint64_t delta = 0;
+  uint32_t ve = 0;
+  if (expire == 0) {
+    flag |= 2u;
+  } else {
+    if (expire < d.base_time) return fail(BCW_ENC_ERR_EXPIRE);
+    delta = expire - d.base_time;
+    if (delta >= (1ull << 35)) return fail(BCW_ENC_ERR_PANIC);
+    ve = uvlen(delta);
+  }
+  const uint32_t hn = 2 + d.ns + uvlen(kl) + uvlen(vl) + uvlen(ml) + el + ve;
+  const uint64_t total = (uint64_t)hn + kl + vl + ml;
+  if (total >> 32) return fail(kClsBatch);
+  uint8_t* p = lit + i * (uint64_t)d.lstride;
+  uint32_t o = 0;
+  p[o++] = (uint8_t)hn;
+  for (uint32_t b = 0; b < d.ns; ++b) p[o++] = d.keys[k0 + b];
+  p[o++] = (uint8_t)flag;
+  o += uvput(p + o, kl);
+  o += uvput(p + o, vl);
+  o += uvput(p + o, ml);
+  for (uint32_t b = 0; b < el; ++b) p[o++] = d.etags[i * (uint64_t)d.etag + b];
+  if (ve) o += uvput(p + o, delta);
+  hlen[i] = hn;
+  sz[i] = (uint32_t)total;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_put_plan: the accepted word and the result. The layout ran over the records before the first error; a batch with
+// an error appends nothing (wal_end = wal_pos).
+__global__ void k_put_plan(PutDev d, uint64_t* __restrict__ emisc, bcw_write_result* __restrict__ r) {
+  const uint64_t err = emisc[kXErr];
+  const bool bad = (err >> 2) < d.n;
+  const uint64_t end = (bad || d.n == 0) ? d.wal_pos : emisc[kXLayEnd];
+  bcw_write_result o{};
+  o.wal_end = end;
+  o.wal_need = end - d.wal_pos;
+  o.fits = o.wal_need <= d.wal_cap ? 1u : 0u;
+  o.err_record = -1;
+  if (bad) {
+    const uint32_t cls = (uint32_t)(err & 3u);
+    o.err_class = cls == kClsBatch ? BCW_ENC_ERR_BATCH : (int32_t)cls;
+    o.err_record = (int64_t)(err >> 2);
+  }
+  const bool acc = !bad && o.fits;
+  o.n_written = acc ? d.n : 0;
+  emisc[P_ACC] = acc ? 1 : 0;
+  emisc[P_NIN] = acc ? d.n : 0;
+  *r = o;
+}
+
+// wave-aggregated add of v to *ctr; returns this lane's exclusive offset
+__device__ __forceinline__ uint64_t wave_alloc(uint64_t* ctr, uint64_t v) {
+  const uint32_t lane = threadIdx.x & 63u;
+  uint64_t incl = v;
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) {
+    const uint64_t t = __shfl_up(incl, s, 64);
+    if (lane >= (uint32_t)s) incl += t;
+  }
+  const uint64_t tot = __shfl(incl, 63, 64);
+  uint64_t base = 0;
+  if (lane == 63 && tot) base = atomicAdd(reinterpret_cast<unsigned long long*>(ctr), (unsigned long long)tot);
+  base = __shfl(base, 63, 64);
+  return base + incl - v;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_put_frags: per accepted record, locs (rec_off, rec_size: db_impl.go:475-476) and its output fragments: the
+// writer's loop (wal.go:505-549) from the record's first header, one fragment per block it touches (a block with
+// exactly 7 bytes left takes the zero-length First). The list's order is arbitrary: a fragment is self-contained.
+__global__ __launch_bounds__(256) void k_put_frags(PutDev d, const uint32_t* __restrict__ sz,
+                                                    const uint64_t* __restrict__ dpos, uint64_t* __restrict__ emisc,
+                                                    PFrag* __restrict__ frags, uint64_t fcap) {
+  const uint64_t j = blockIdx.x * 256ull + threadIdx.x;
+  const bool on = emisc[P_ACC] != 0 && j < d.n;
+  uint64_t P = 0, len = 0, cnt = 0;
+  if (on) {
+    P = dpos[j];
+    len = sz[j];
+    const uint64_t x1 = blk_end(P) - (P + kHdr);  // room in the first block
+    cnt = len <= x1 ? 1 : 1 + (len - x1 + kM - 1) / kM;
+  }
+  uint64_t f = wave_alloc(&emisc[P_NFRAG], cnt);
+  if (!on) return;
+  d.rec_off[j] = P;
+  d.rec_size[j] = len;
+  if (f + cnt > fcap) {  // the host sizes the list from bcw_write_bound: never expected
+    atomicOr(reinterpret_cast<unsigned long long*>(&emisc[P_FOVER]), 1ull);
+    return;
+  }
+  uint64_t hp = P, x0 = 0;
+  for (bool first = true;; first = false) {
+    const uint64_t be = blk_end(hp), ds = hp + kHdr;
+    const uint64_t rem = len - x0;
+    const uint64_t flen = rem < be - ds ? rem : be - ds;
+    const bool last = flen == rem;
+    const uint32_t type = first ? (last ? BCW_RECORD_FULL : BCW_RECORD_FIRST) : (last ? BCW_RECORD_LAST : BCW_RECORD_MIDDLE);
+    frags[f++] = PFrag{hp, (uint32_t)j, (uint32_t)x0, (uint32_t)flen, type};
+    x0 += flen;
+    if (last) break;
+    hp = be;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_put_write. One wave per output fragment; lane l takes the fragment's 16 B output units l, l + 64, ... (units
+// aligned to the output address, so interior units are one aligned 16 B store; the first and last unit of a fragment
+// may be partial and are stored bytewise). A unit's bytes come from up to four inputs -- the record's header literal,
+// key, value and meta -- each at its own byte alignment: per input an aligned pair of 16 B loads and a byte shift
+// (shift16), where a granule of an input is loaded only when it holds a byte the unit needs, so no load touches a
+// granule without a byte of the record's own range and none goes past an input's end (a boundary unit's unused load
+// slots read the record's own literal slot in the scratch, gather_unit).
+// CRC: each lane keeps a Horner chain c = A_{8*1024}(c) ^ R(unit) over its units (R: raw CRC-32C, init 0, bytes
+// outside the fragment read as 0: leading zeros do not change R), the chains are shifted to the end of the last unit
+// (A_{8*16*dn}, dn < 64 units follow the lane's last one), XOR-ed over the wave, the zero bytes after the fragment's
+// end are undone by A_{8t}^-1, and A_{8 flen}(~0) (initc) supplies the init value. Lanes 0-6 store the header:
+// ComputeCRC32 (utils.go:24-29), length, type.
+// LDS (32.5 KiB per workgroup of 8 waves, 2 workgroups per CU at the kernel's registers): the slice-by-8 byte tables
+// t8, the round operator A_{8*1024} as byte images, and the nibble-image operators of the final shift, laid out as
+// k_write's (bcw_encode.hip). Every table read is a ds_read_b32: 32 banks of 4 bytes, a wave
+// served as two halves of 32 lanes. Operator tables are kOpStride = 144 words apart, i.e. 16 banks apart, and one
+// nibble row is 16 words, so lanes applying different operators (different dn) in the final shift collide only on
+// equal nibbles. The byte-table reads are data-dependent: 32 lanes on random banks of 32, a few ways of conflict
+// on average, which no static layout removes; replicating the 8 KiB table per lane group would, at the price of the
+// occupancy the gather's loads need, and is not done here (k_write made the same choice).
+constexpr int kPT = 512;
+constexpr int kOpStride = 144;
+#ifndef BCW_PUT_ROUNDS
+#define BCW_PUT_ROUNDS 2
+#endif
+constexpr int kPutRounds = BCW_PUT_ROUNDS;  // units per lane whose source loads are in flight together
+constexpr int kNOps = 21;  // A_{8*16*n} (n < 16), A_{8*256*n} (n < 5): [20] = A_{8*1024}, one round of the wave
+
+struct WArgs {
+  PutDev d;
+  const uint64_t* emisc;
+  const PFrag* frags;
+  uint64_t fcap;
+  const uint32_t* sz;
+  const uint64_t* dpos;
+  const uint8_t* lit;
+  const uint32_t* hlen;
+  const uint32_t* wops;   // enc_ops (layout in bcw_internal.h)
+  const uint32_t* initc;  // A_{8L}(0xFFFFFFFF)
+};
+
+__device__ __forceinline__ uint32_t op_apply(const uint32_t* __restrict__ op, uint32_t x) {
+  uint32_t r = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) r ^= op[i * 16 + ((x >> (4 * i)) & 15u)];
+  return r;
+}
+// the same with byte images (4 x 256 words)
+__device__ __forceinline__ uint32_t op_apply_b(const uint32_t* __restrict__ op, uint32_t x) {
+  return op[x & 0xffu] ^ op[256 + ((x >> 8) & 0xffu)] ^ op[512 + ((x >> 16) & 0xffu)] ^ op[768 + (x >> 24)];
+}
+// CRC-32C state after 16 more bytes (raw, slice-by-8: t8[256 k + b] = CRC of byte b and k zeros)
+__device__ __forceinline__ uint32_t crc_step16(const uint32_t* __restrict__ t8, uint32_t c, uint4 v) {
+  uint32_t x = c ^ v.x, y = v.y;
+  c = t8[1792 + (x & 0xffu)] ^ t8[1536 + ((x >> 8) & 0xffu)] ^ t8[1280 + ((x >> 16) & 0xffu)] ^ t8[1024 + (x >> 24)] ^
+      t8[768 + (y & 0xffu)] ^ t8[512 + ((y >> 8) & 0xffu)] ^ t8[256 + ((y >> 16) & 0xffu)] ^ t8[y >> 24];
+  x = c ^ v.z;
+  y = v.w;
+  return t8[1792 + (x & 0xffu)] ^ t8[1536 + ((x >> 8) & 0xffu)] ^ t8[1280 + ((x >> 16) & 0xffu)] ^ t8[1024 + (x >> 24)] ^
+         t8[768 + (y & 0xffu)] ^ t8[512 + ((y >> 8) & 0xffu)] ^ t8[256 + ((y >> 16) & 0xffu)] ^ t8[y >> 24];
+}
+__device__ __forceinline__ uint32_t sel_byte(uint4 v, uint32_t b) {
+  const uint32_t w = (b & 8u) ? ((b & 4u) ? v.w : v.z) : ((b & 4u) ? v.y : v.x);
+  return (w >> (8 * (b & 3u))) & 0xffu;
+}
+// bytes [lo, hi) of a 16 B unit
+__device__ __forceinline__ uint4 range_mask(int32_t lo, int32_t hi) {
+  uint32_t m[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int32_t a = min(max(lo - 4 * k, 0), 4), b = min(max(hi - 4 * k, 0), 4);
+    m[k] = (uint32_t)(((1ull << (8 * b)) - 1) & ~((1ull << (8 * a)) - 1));
+  }
+  return make_uint4(m[0], m[1], m[2], m[3]);
+}
+// the 16 bytes at address a, of which only bytes [lo, hi) are needed (0 <= lo < hi <= 16) and known to lie inside
+// the input: the aligned granule at a & ~15 is loaded when it holds one of them, and so is the next one
+__device__ __forceinline__ uint4 load_unit(uint64_t a, int32_t lo, int32_t hi) {
+  const uint32_t sh = (uint32_t)(a & 15u);
+  const uint4* g = reinterpret_cast<const uint4*>((uintptr_t)(a & ~15ull));
+  const uint4 z = make_uint4(0, 0, 0, 0);
+  const uint4 v0 = (int32_t)sh + lo < 16 ? g[0] : z;
+  const uint4 v1 = (int32_t)sh + hi > 16 ? g[1] : z;
+  return shift16(v0, v1, sh);
+}
+__device__ __forceinline__ void or_masked(uint4& v, uint4 q, uint4 m) {
+  v.x |= q.x & m.x;
+  v.y |= q.y & m.y;
+  v.z |= q.z & m.z;
+  v.w |= q.w & m.w;
+}
+
+// a record's payload as four inputs: input s covers payload offsets [z[s], z[s + 1]) and starts at address a[s]
+struct Rec4 {
+  int64_t z[5];
+  uint64_t a[4];
+};
+// bytes [b0, b1) of the unit whose byte 0 is payload offset zb (the other bytes 0)
+__device__ __forceinline__ uint4 gather_unit(const Rec4& R, int64_t zb, int32_t b0, int32_t b1) {
+  const int64_t lo = zb + b0, hi = zb + b1;
+  // the usual unit lies inside the value
+  if (lo >= R.z[2] && hi <= R.z[3]) {
+    const uint4 q = load_unit(R.a[2] + (uint64_t)(zb - R.z[2]), b0, b1);
+    if (b1 - b0 == 16) return q;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    or_masked(v, q, range_mask(b0, b1));
+    return v;
+  }
+  // a unit at an input boundary: the loads of all four inputs are issued before any is used (one memory latency,
+  // not four). An input the unit does not touch loads the record's literal slot instead, which is always there.
+  uint4 g0[4], g1[4];
+  int32_t u0[4], u1[4];
+  uint32_t sh[4];
+  const uint64_t spare = R.a[0] & ~15ull;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int64_t s0 = max(lo, R.z[s]), s1 = min(hi, R.z[s + 1]);
+    const bool need = s0 < s1;
+    u0[s] = need ? (int32_t)(s0 - zb) : 0;
+    u1[s] = need ? (int32_t)(s1 - zb) : 0;
+    const uint64_t a = R.a[s] + (uint64_t)(zb - R.z[s]);
+    sh[s] = (uint32_t)(a & 15u);
+    const uint64_t Ba = a & ~15ull;
+    const bool n0 = need && (int32_t)sh[s] + u0[s] < 16, n1 = need && (int32_t)sh[s] + u1[s] > 16;
+    g0[s] = *reinterpret_cast<const uint4*>((uintptr_t)(n0 ? Ba : spare));
+    g1[s] = *reinterpret_cast<const uint4*>((uintptr_t)(n1 ? Ba + 16 : spare));
+  }
+  uint4 v = make_uint4(0, 0, 0, 0);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) or_masked(v, shift16(g0[s], g1[s], sh[s]), range_mask(u0[s], u1[s]));
+  return v;
+}
+
+__global__ __launch_bounds__(kPT) void k_put_write(WArgs A) {
+  const PutDev& d = A.d;
+  const uint64_t nfr = A.emisc[P_ACC] ? (A.emisc[P_NFRAG] < A.fcap ? A.emisc[P_NFRAG] : A.fcap) : 0;
+  if ((uint64_t)blockIdx.x * (kPT / 64) >= nfr) return;  // rejected batch, or no fragment for this workgroup
+  __shared__ uint32_t t8[8 * 256];
+  __shared__ uint32_t sop[kNOps * kOpStride];
+  __shared__ uint32_t sinv[16 * 128];  // A_{8t}^-1
+  __shared__ uint32_t hopb[4 * 256];   // A_{8*1024} as byte images: the Horner step of every unit in 4 lookups, not 8
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  for (uint32_t i = tid; i < 256; i += kPT) {
+    uint32_t c = i;
+    for (int b = 0; b < 8; ++b) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
+    t8[i] = c;
+  }
+  for (uint32_t i = tid; i < kNOps * 128; i += kPT) sop[(i >> 7) * kOpStride + (i & 127u)] = A.wops[i];
+  for (uint32_t i = tid; i < 16 * 128; i += kPT) sinv[i] = A.wops[kOpInv * 128 + i];
+  __syncthreads();
+  for (uint32_t i = tid; i < 256; i += kPT) {
+    uint32_t c = t8[i];
+    for (int k = 1; k < 8; ++k) { c = (c >> 8) ^ t8[c & 0xffu]; t8[256 * k + i] = c; }
+  }
+  __syncthreads();
+  {
+    const uint32_t* hop = sop + 20 * kOpStride;  // A_{8*1024}, nibble images
+    for (uint32_t i = tid; i < 4 * 256; i += kPT) {
+      const uint32_t k = i >> 8, b = i & 255u;
+      hopb[i] = hop[(2 * k) * 16 + (b & 15u)] ^ hop[(2 * k + 1) * 16 + (b >> 4)];
+    }
+  }
+  __syncthreads();
+  const uint64_t nw = (uint64_t)gridDim.x * (kPT / 64);
+  const uint64_t obase = (uint64_t)(uintptr_t)d.out;
+  // the wave's index as a scalar: the fragment descriptor and the record's offsets are then wave-uniform (scalar
+  // loads into SGPRs, not 64 copies in VGPRs)
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  for (uint64_t f = (uint64_t)blockIdx.x * (kPT / 64) + wv; f < nfr; f += nw) {
+    const PFrag F = A.frags[f];
+    const uint64_t i = F.rec, hp = F.hp, flen = F.flen;
+    // defensive: the fragment lies inside the output (the layout and the plan guarantee it)
+    if (hp < d.wal_pos || hp + kHdr + flen - d.wal_pos > d.wal_cap) continue;
+    // zero pad before a record that starts a block (wal.go:509-512; at most 6 bytes)
+    if (F.x0 == 0 && (F.type == BCW_RECORD_FULL || F.type == BCW_RECORD_FIRST) && (hp - 40) % kL == 0) {
+      const uint64_t prev = i == 0 ? d.wal_pos : rec_end(A.dpos[i - 1], A.sz[i - 1]);
+      if (lane < kHdr && prev + lane < hp) d.out[prev + lane - d.wal_pos] = 0;
+    }
+    uint32_t acc = 0;
+    if (flen) {
+      Rec4 R;
+      const uint64_t k0 = d.koff[i], k1 = d.koff[i + 1], v0 = d.voff[i], v1 = d.voff[i + 1], m0 = d.moff[i],
+                     m1 = d.moff[i + 1];
+      R.z[0] = 0;
+      R.z[1] = A.hlen[i];
+      R.z[2] = R.z[1] + (int64_t)(k1 - k0 - d.ns);
+      R.z[3] = R.z[2] + (int64_t)(v1 - v0);
+      R.z[4] = R.z[3] + (int64_t)(m1 - m0);
+      R.a[0] = (uint64_t)(uintptr_t)(A.lit + i * (uint64_t)d.lstride);
+      R.a[1] = (uint64_t)(uintptr_t)d.keys + k0 + d.ns;
+      R.a[2] = (uint64_t)(uintptr_t)d.vals + v0;
+      R.a[3] = (uint64_t)(uintptr_t)d.metas + m0;
+      const uint64_t as = obase + (hp + kHdr - d.wal_pos), ae = as + flen;  // output addresses of the data
+      const uint64_t uf = as >> 4, ul = (ae - 1) >> 4;
+      const uint32_t nunits = (uint32_t)(ul - uf + 1);
+      uint32_t c = 0;
+      // kPutRounds units per lane are in flight together: first the aligned loads of the units that lie whole inside
+      // the value (the usual unit), then, unit by unit, the byte shift (or the general gather), the store and the CRC
+      for (uint32_t r0 = lane; r0 < nunits; r0 += 64 * kPutRounds) {
+        uint4 g0[kPutRounds], g1[kPutRounds];
+        uint32_t shv[kPutRounds];
+        bool fast[kPutRounds];
+#pragma unroll
+        for (int q = 0; q < kPutRounds; ++q) {
+          const uint32_t r = r0 + 64 * q;
+          const uint64_t ua = (uf + r) << 4;
+          const int64_t zb = (int64_t)F.x0 + ((int64_t)ua - (int64_t)as);  // payload offset of unit byte 0
+          fast[q] = r < nunits && ua >= as && ua + 16 <= ae && zb >= R.z[2] && zb + 16 <= R.z[3];
+          shv[q] = 0;
+          g0[q] = g1[q] = make_uint4(0, 0, 0, 0);
+          if (fast[q]) {
+            const uint64_t a = R.a[2] + (uint64_t)(zb - R.z[2]);
+            const uint4* g = reinterpret_cast<const uint4*>((uintptr_t)(a & ~15ull));
+            shv[q] = (uint32_t)(a & 15u);
+            g0[q] = g[0];
+            if (shv[q]) g1[q] = g[1];  // 16 bytes from an unaligned address end in the next granule
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < kPutRounds; ++q) {
+          const uint32_t r = r0 + 64 * q;
+          if (r >= nunits) continue;
+          const uint64_t ua = (uf + r) << 4;
+          const int32_t b0 = ua < as ? (int32_t)(as - ua) : 0;
+          const int32_t b1 = ua + 16 > ae ? (int32_t)(ae - ua) : 16;
+          const int64_t zb = (int64_t)F.x0 + ((int64_t)ua - (int64_t)as);
+          const uint4 v = fast[q] ? shift16(g0[q], g1[q], shv[q]) : gather_unit(R, zb, b0, b1);
+          uint8_t* q8 = reinterpret_cast<uint8_t*>((uintptr_t)ua);
+          if (b1 - b0 == 16) {
+            __builtin_nontemporal_store(v.x, reinterpret_cast<uint32_t*>(q8));
+            __builtin_nontemporal_store(v.y, reinterpret_cast<uint32_t*>(q8) + 1);
+            __builtin_nontemporal_store(v.z, reinterpret_cast<uint32_t*>(q8) + 2);
+            __builtin_nontemporal_store(v.w, reinterpret_cast<uint32_t*>(q8) + 3);
+          } else {
+            for (int32_t b = b0; b < b1; ++b) q8[b] = (uint8_t)sel_byte(v, (uint32_t)b);
+          }
+          c = op_apply_b(hopb, c) ^ crc_step16(t8, 0u, v);
+        }
+      }
+      // shift each lane's chain to the end of the fragment's last unit (dn < 64 units follow the lane's last one)
+      if (lane < nunits) {
+        const uint32_t dn = (nunits - 1 - lane) & 63u;
+        if (dn & 15u) c = op_apply(sop + (dn & 15u) * kOpStride, c);
+        if (dn >> 4) c = op_apply(sop + (16u + (dn >> 4)) * kOpStride, c);
+      }
+#pragma unroll
+      for (int m = 1; m < 64; m <<= 1) c ^= __shfl_xor(c, m, 64);
+      const uint32_t t = (uint32_t)(((ul + 1) << 4) - ae);
+      acc = t ? op_apply(sinv + t * 128, c) : c;
+    }
+    if (lane < kHdr) {
+      const uint32_t crc = ~(acc ^ A.initc[flen]);
+      const uint32_t masked = ((crc >> 15) | (crc << 17)) + 0xa282ead8u;  // ComputeCRC32 (utils.go:24-29)
+      const uint32_t by = lane < 4 ? (masked >> (8 * lane)) : lane == 4 ? (uint32_t)flen : lane == 5 ? (uint32_t)(flen >> 8) : F.type;
+      d.out[hp - d.wal_pos + lane] = (uint8_t)by;
+    }
+  }
+}
+
+}  // namespace put
+
+void put_scratch_free(PutScratch& s) {
+  (void)hipFree(s.lit);
+  (void)hipFree(s.hlen);
+  (void)hipFree(s.frags);
+  s = PutScratch{};
+}
+
+namespace {
+
+int put_scratch_reserve(bcw_ctx* c, uint64_t rows, uint64_t lit_bytes, uint64_t nfrags) {
+  PutScratch& s = c->ps;
+  if (rows <= s.rows_cap && lit_bytes <= s.lit_cap && nfrags <= s.frag_cap) return BCW_OK;
+  (void)hipStreamSynchronize(c->cur);
+  const uint64_t r = std::max(rows, s.rows_cap), l = std::max(lit_bytes, s.lit_cap), f = std::max(nfrags, s.frag_cap);
+  const int wr = s.write_resident;
+  put_scratch_free(s);
+  if (hipMalloc(&s.lit, l) != hipSuccess || hipMalloc(&s.hlen, r * 4) != hipSuccess ||
+      hipMalloc(&s.frags, f * sizeof(put::PFrag)) != hipSuccess) {
+    put_scratch_free(s);
+    return BCW_E_NOMEM;
+  }
+  s.write_resident = wr;
+  s.rows_cap = r;
+  s.lit_cap = l;
+  s.frag_cap = f;
+  return BCW_OK;
+}
+
+// payload bytes Record.Encode adds to a record's key, value and meta: headerSize, flags, three varints of at most
+// 5 bytes, the etag, the expire varint (ns is part of the merged key)
+uint64_t enc_overhead(uint32_t etag_size) { return 2 + 15 + (uint64_t)etag_size + 5; }
+
+}  // namespace
+}  // namespace bcw
+
+using namespace bcw;
+
+extern "C" {
+
+uint64_t bcw_write_bound(uint64_t n, uint64_t keys_len, uint64_t vals_len, uint64_t metas_len, uint32_t etag_size,
+                         uint64_t wal_pos) {
+  (void)wal_pos;  // the bound holds for every phase of wal_pos in the block grid
+  // payloads + per record one header (7) and one pad (<= 6) + the leading pad (<= 6). With B bytes appended over nb
+  // blocks: B <= raw + 7 nb (one continuation or zero-length-First header per block) and nb <= B / 32768 + 2, so
+  // B <= (raw + 14) * 32768 / 32761.
+  const uint64_t raw = keys_len + vals_len + metas_len + n * (enc_overhead(etag_size) + 13) + 6 + 14;
+  return raw + (raw / (kBlock - kHdr) + 1) * kHdr;
+}
+
+int64_t bcw_record_encode(uint8_t* out, uint64_t cap, const uint8_t* merged_key, uint64_t key_len, const uint8_t* val,
+                          uint64_t val_len, const uint8_t* meta, uint64_t meta_len, const uint8_t* etag,
+                          uint64_t expire, uint32_t flags, uint32_t etag_size, uint64_t base_time, uint32_t ns_size) {
+  auto uvput = [](uint8_t* p, uint64_t v) {
+    uint32_t n = 0;
+    while (v >= 0x80) { p[n++] = (uint8_t)(v | 0x80); v >>= 7; }
+    p[n++] = (uint8_t)v;
+    return n;
+  };
+  if (key_len < ns_size || (key_len | val_len | meta_len) >> 32) return -BCW_ENC_ERR_BATCH;
+  const uint32_t el = (flags & BCW_WR_ETAG) ? etag_size : 0u;
+  if (el && !etag) return -BCW_ENC_ERR_BATCH;
+  uint8_t flag = (uint8_t)((el == 0 ? 1u : 0u) | ((flags & BCW_WR_TOMBSTONE) ? 4u : 0u));
+  uint8_t exp[10], tmp[30];
+  uint32_t ve = 0;
+  if (expire == 0) flag |= 2u;
+  else if (expire < base_time) return -BCW_ENC_ERR_EXPIRE;
+  else if (expire - base_time >= (1ull << 35)) return -BCW_ENC_ERR_PANIC;
+  else ve = uvput(exp, expire - base_time);
+  const uint64_t kl = key_len - ns_size;
+  uint32_t t = uvput(tmp, kl);
+  t += uvput(tmp + t, val_len);
+  t += uvput(tmp + t, meta_len);
+  const uint64_t hn = 2ull + ns_size + t + el + ve;
+  const uint64_t total = hn + kl + val_len + meta_len;
+  if (total >> 32) return -BCW_ENC_ERR_BATCH;
+  if (total > cap || !out) return -BCW_ENC_ERR_TABLE;
+  uint64_t o = 0;
+  auto app = [&](const uint8_t* p, uint64_t n) {
+    if (n) memcpy(out + o, p, n);
+    o += n;
+  };
+  out[o++] = (uint8_t)hn;  // byte(headerSize): truncates above 255 (record.go:109)
+  app(merged_key, ns_size);
+  out[o++] = flag;
+  app(tmp, t);
+  app(etag, el);
+  app(exp, ve);
+  app(merged_key + ns_size, kl);
+  app(val, val_len);
+  app(meta, meta_len);
+  return (int64_t)o;
+}
+
+int bcw_write_records_async(bcw_index* ix, const bcw_write_params* p, const bcw_write_batch* b, const bcw_write_out* o,
+                            bcw_write_result* d_result) {
+  if (!ix || !p || !b || !o || !d_result) return BCW_E_INVAL;
+  if (p->wal_pos < BCW_SUPER_BLOCK_SIZE || p->ns_size > 0xffffu || p->etag_size > 0xffffu) return BCW_E_INVAL;
+  const uint64_t n = b->n;
+  if (n >= 0xffffff00ull) return BCW_E_INVAL;  // u32 record ids
+  if (n && (!b->key_off || !b->val_off || !b->meta_off || !b->expire || !b->flags || !o->rec_off || !o->rec_size))
+    return BCW_E_INVAL;
+  if ((b->keys_len && !b->keys) || (b->vals_len && !b->vals) || (b->metas_len && !b->metas) || (o->wal_cap && !o->wal))
+    return BCW_E_INVAL;
+  const bool stat = o->found || o->free_fid || o->free_bytes;
+  if (stat && !(o->found && o->free_fid && o->free_bytes)) return BCW_E_INVAL;
+  bcw_ctx* c = index_ctx(ix);
+  DeviceGuard dg(c->device);
+  if (!dg.ok) return BCW_E_HIP;
+  const uint32_t lstride = (uint32_t)((enc_overhead(p->etag_size) + p->ns_size + 15) & ~15ull);
+  const uint64_t bound = bcw_write_bound(n, b->keys_len, b->vals_len, b->metas_len, p->etag_size, p->wal_pos);
+  const uint64_t fcap = n + bound / kBlock + 2;  // every fragment after a record's first one starts a block
+  int rc = enc_scratch_reserve(c, std::max<uint64_t>(n, 1));
+  if (rc == BCW_OK) rc = put_scratch_reserve(c, std::max<uint64_t>(n, 1), std::max<uint64_t>(n, 1) * lstride, fcap);
+  if (rc != BCW_OK) return rc;
+  hipStream_t st = c->cur;
+  EncScratch& es = c->es;
+  PutScratch& ps = c->ps;
+  Prof& pr = c->prof;
+  hipEvent_t ev = nullptr;
+
+  put::PutDev d{};
+  d.n = n;
+  d.keys = b->keys;
+  d.vals = b->vals;
+  d.metas = b->metas;
+  d.etags = b->etags;
+  d.flags = b->flags;
+  d.koff = b->key_off;
+  d.voff = b->val_off;
+  d.moff = b->meta_off;
+  d.expire = b->expire;
+  d.keys_len = b->keys_len;
+  d.vals_len = b->vals_len;
+  d.metas_len = b->metas_len;
+  d.base_time = p->base_time;
+  d.wal_pos = p->wal_pos;
+  d.wal_cap = o->wal_cap;
+  d.out = o->wal;
+  d.rec_off = o->rec_off;
+  d.rec_size = o->rec_size;
+  d.ns = p->ns_size;
+  d.etag = p->etag_size;
+  d.lstride = lstride;
+  const uint32_t grid = (uint32_t)((n + 255) / 256);
+
+  enc_layout_reset(es, st);
+  if (n) {
+    pr.begin(K_PUT_PREP, st, ev);
+    put::k_put_prep<<<grid, 256, 0, st>>>(d, es.sz, ps.lit, ps.hlen, es.emisc);
+    pr.end(K_PUT_PREP, st, ev);
+    pr.begin(K_PUT_LAYOUT, st, ev);
+    if (enc_layout_run(es, n, p->wal_pos, st) != hipSuccess) return BCW_E_HIP;
+    pr.end(K_PUT_LAYOUT, st, ev);
+  }
+  pr.begin(K_PUT_FRAGS, st, ev);
+  put::k_put_plan<<<1, 1, 0, st>>>(d, es.emisc, d_result);
+  if (n) put::k_put_frags<<<grid, 256, 0, st>>>(d, es.sz, es.dpos, es.emisc, static_cast<put::PFrag*>(ps.frags), fcap);
+  pr.end(K_PUT_FRAGS, st, ev);
+  if (n) {
+    put::WArgs W{};
+    W.d = d;
+    W.emisc = es.emisc;
+    W.frags = static_cast<const put::PFrag*>(ps.frags);
+    W.fcap = fcap;
+    W.sz = es.sz;
+    W.dpos = es.dpos;
+    W.lit = ps.lit;
+    W.hlen = ps.hlen;
+    W.wops = c->tabs.enc_ops;
+    W.initc = c->tabs.initc;
+    // a grid of resident workgroups: each wave walks the fragment list with the grid's stride, and the tables are
+    // built a bounded number of times however long the list is
+    const uint64_t want = (fcap + put::kPT / 64 - 1) / (put::kPT / 64);
+    if (ps.write_resident == 0 &&
+        (hipOccupancyMaxActiveBlocksPerMultiprocessor(&ps.write_resident, put::k_put_write, put::kPT, 0) != hipSuccess ||
+         ps.write_resident < 1))
+      ps.write_resident = 2;
+    const uint32_t wgrid =
+        (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)c->num_cus * ps.write_resident));
+    pr.begin(K_PUT_WRITE, st, ev);
+    put::k_put_write<<<wgrid, put::kPT, 0, st>>>(W);
+    pr.end(K_PUT_WRITE, st, ev);
+  }
+  if (hipGetLastError() != hipSuccess) return BCW_E_HIP;
+  PutIx q{};
+  q.n = n;
+  q.keys = b->keys;
+  q.koff = b->key_off;
+  q.keys_len = b->keys_len;
+  q.n_in = es.emisc + put::P_NIN;
+  q.rec_off = o->rec_off;
+  q.rec_size = o->rec_size;
+  q.flags = b->flags;
+  q.fid = p->fid;
+  q.found = o->found;
+  q.free_fid = o->free_fid;
+  q.free_bytes = o->free_bytes;
+  q.idx_err = &d_result->idx_err;
+  pr.begin(K_PUT_INDEX, st, ev);
+  rc = ix_put_batch(ix, q);
+  pr.end(K_PUT_INDEX, st, ev);
+  return rc;
+}
+
+int bcw_write_records(bcw_index* ix, const bcw_write_params* p, const bcw_write_batch* hb, const bcw_write_out* ho,
+                      bcw_write_result* h_result) {
+  if (!ix || !p || !hb || !ho || !h_result) return BCW_E_INVAL;
+  const uint64_t n = hb->n;
+  if (n && (!hb->key_off || !hb->val_off || !hb->meta_off || !hb->expire || !hb->flags || !ho->rec_off || !ho->rec_size))
+    return BCW_E_INVAL;
+  if (ho->wal_cap && !ho->wal) return BCW_E_INVAL;
+  const bool stat = ho->found || ho->free_fid || ho->free_bytes;
+  if (stat && !(ho->found && ho->free_fid && ho->free_bytes)) return BCW_E_INVAL;
+  *h_result = bcw_write_result{};
+  uint64_t kb = 0, vb = 0, mb = 0;
+  bool any_etag = false;
+  if (n) {
+    for (uint64_t i = 0; i < n; ++i) {
+      if (hb->key_off[i + 1] < hb->key_off[i] || hb->val_off[i + 1] < hb->val_off[i] ||
+          hb->meta_off[i + 1] < hb->meta_off[i])
+        return BCW_E_INVAL;
+      any_etag = any_etag || (hb->flags[i] & BCW_WR_ETAG);
+    }
+    kb = hb->key_off[n] - hb->key_off[0];
+    vb = hb->val_off[n] - hb->val_off[0];
+    mb = hb->meta_off[n] - hb->meta_off[0];
+    if ((kb && !hb->keys) || (vb && !hb->vals) || (mb && !hb->metas)) return BCW_E_INVAL;
+    if (any_etag && p->etag_size && !hb->etags) return BCW_E_INVAL;
+  }
+  bcw_ctx* c = index_ctx(ix);
+  DeviceGuard dg(c->device);
+  if (!dg.ok) return BCW_E_HIP;
+  const uint64_t eb = (any_etag && hb->etags) ? n * (uint64_t)p->etag_size : 0;
+  auto r16 = [](uint64_t v) { return (v + 15) & ~15ull; };
+  // keys | values | metas | etags | wal | three offset arrays, expire | rec_off, rec_size, free_fid, free_bytes |
+  // flags, found | result
+  const uint64_t bytes = r16(kb) + r16(vb) + r16(mb) + r16(eb) + r16(ho->wal_cap) + 3 * 8 * (n + 1) + 8 * n + 32 * n +
+                         r16(n) + r16(n) + sizeof(bcw_write_result) + 64;
+  void* mem = nullptr;
+  if (hipMalloc(&mem, bytes) != hipSuccess) return BCW_E_NOMEM;
+  uint8_t* m = (uint8_t*)mem;
+  bcw_write_batch db{};
+  bcw_write_out d{};
+  db.n = n;
+  uint8_t* d_keys = m; m += r16(kb);
+  uint8_t* d_vals = m; m += r16(vb);
+  uint8_t* d_metas = m; m += r16(mb);
+  uint8_t* d_etags = m; m += r16(eb);
+  d.wal = m; m += r16(ho->wal_cap);
+  d.wal_cap = ho->wal_cap;
+  uint64_t* d_koff = (uint64_t*)m; m += 8 * (n + 1);
+  uint64_t* d_voff = (uint64_t*)m; m += 8 * (n + 1);
+  uint64_t* d_moff = (uint64_t*)m; m += 8 * (n + 1);
+  uint64_t* d_exp = (uint64_t*)m; m += 8 * n;
+  d.rec_off = (uint64_t*)m; m += 8 * n;
+  d.rec_size = (uint64_t*)m; m += 8 * n;
+  uint64_t* d_ffid = (uint64_t*)m; m += 8 * n;
+  uint64_t* d_fbytes = (uint64_t*)m; m += 8 * n;
+  uint8_t* d_flags = m; m += r16(n);
+  uint8_t* d_found = m; m += r16(n);
+  bcw_write_result* d_res = (bcw_write_result*)m;
+  if ((uint8_t*)(d_res + 1) > (uint8_t*)mem + bytes) {  // the carve-up above must stay inside the allocation
+    (void)hipFree(mem);
+    return BCW_E_INVAL;
+  }
+  if (stat) { d.found = d_found; d.free_fid = d_ffid; d.free_bytes = d_fbytes; }
+  db.keys = kb ? d_keys : nullptr;
+  db.key_off = d_koff;
+  db.keys_len = kb;
+  db.vals = vb ? d_vals : nullptr;
+  db.val_off = d_voff;
+  db.vals_len = vb;
+  db.metas = mb ? d_metas : nullptr;
+  db.meta_off = d_moff;
+  db.metas_len = mb;
+  db.etags = eb ? d_etags : nullptr;
+  db.expire = d_exp;
+  db.flags = d_flags;
+  hipStream_t st = c->cur;
+  std::vector<uint64_t> off(3 * (n + 1));
+  for (uint64_t i = 0; n && i <= n; ++i) {
+    off[i] = hb->key_off[i] - hb->key_off[0];
+    off[n + 1 + i] = hb->val_off[i] - hb->val_off[0];
+    off[2 * (n + 1) + i] = hb->meta_off[i] - hb->meta_off[0];
+  }
+  auto up = [&](void* dst, const void* src, uint64_t nb) {
+    return nb == 0 || hipMemcpyAsync(dst, src, nb, hipMemcpyHostToDevice, st) == hipSuccess;
+  };
+  auto down = [&](void* dst, const void* src, uint64_t nb) {
+    return !dst || nb == 0 || hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToHost, st) == hipSuccess;
+  };
+  bool ok = true;
+  if (n)
+    ok = up(d_keys, kb ? hb->keys + hb->key_off[0] : nullptr, kb) &&
+         up(d_vals, vb ? hb->vals + hb->val_off[0] : nullptr, vb) &&
+         up(d_metas, mb ? hb->metas + hb->meta_off[0] : nullptr, mb) && up(d_etags, hb->etags, eb) &&
+         up(d_koff, off.data(), 3 * 8 * (n + 1)) && up(d_exp, hb->expire, 8 * n) && up(d_flags, hb->flags, n);
+  int rc = ok ? bcw_write_records_async(ix, p, &db, &d, d_res) : BCW_E_HIP;
+  if (rc == BCW_OK) {
+    ok = down(h_result, d_res, sizeof(bcw_write_result)) && hipStreamSynchronize(st) == hipSuccess;
+    rc = !ok ? BCW_E_HIP : h_result->fits ? BCW_OK : BCW_E_CAPACITY;
+  }
+  if (rc == BCW_OK && h_result->n_written) {
+    ok = down(ho->wal, d.wal, h_result->wal_need) && down(ho->rec_off, d.rec_off, 8 * n) &&
+         down(ho->rec_size, d.rec_size, 8 * n);
+    if (ok && stat)
+      ok = down(ho->found, d_found, n) && down(ho->free_fid, d_ffid, 8 * n) && down(ho->free_bytes, d_fbytes, 8 * n);
+    if (!ok) rc = BCW_E_HIP;
+  }
+  if (hipStreamSynchronize(st) != hipSuccess && rc == BCW_OK) rc = BCW_E_HIP;
+  (void)hipFree(mem);
+  return rc;
+}
+
+}  // extern "C"

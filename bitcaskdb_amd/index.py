@@ -6,6 +6,7 @@ Names, argument meaning and error behaviour follow wenzhang-dev/bitcaskDB:
   recover_from_wals                        DBImpl.recoverFromWals / recoverFromWal  db_impl.go:268-314
   compact_one_wal_filtered                 compactOneWal with doFilter       compaction.go:294-348
   Index.get_records / WalSet               DBImpl.Get / getWalRef            db_impl.go:567-593, 607-619
+  Index.write (write.py)                   DBImpl.writeWal + writeIndex      db_impl.go:434-480
 The index lives in HBM (bcw_index); every operation goes through the C-ABI, there is no host fallback.
 """
 from __future__ import annotations
@@ -363,6 +364,13 @@ class Index:
             else:
                 out.append(WalError("record length >= 2^32 is not supported by the device table"))
         return out
+
+    # ---- batched Write (DBImpl.Write's writeWal + writeIndex, db_impl.go:434-480) ----
+    def write(self, active, batch, walset=None, ns_size: int = 20, etag_size: int = 20):
+        """append `batch` (write.WriteBatch) to the active WAL's resident image (write.ActiveWal) and apply it to
+        this index, on the device: returns (locs, write_stats {fid: freed bytes}); see write.write_batch"""
+        from .write import write_batch
+        return write_batch(self, active, batch, walset, ns_size, etag_size)
 
     # ---- table-driven (device-resident) Put loops ----
     def recover_segment(self, data, mode: int, fid: int, start_off: int, base_time: int, ns_size: int,

@@ -23,6 +23,10 @@
  *                        plus      getWalRef                    db_impl.go:589-593  (bcw_walset_*)
  *                        plus      readRecord                   db_impl.go:607-619  (Wal.ReadRecord wal.go:556-573,
  *                                                                                    RecordFromBytes record.go:140-239)
+ *   bcw_write_records*   replaces  DBImpl.Write's two steps     db_impl.go:343-431
+ *                        i.e.      writeWal                     db_impl.go:456-480  (Record.Encode record.go:57-138,
+ *                                                                                    Wal.WriteRecord wal.go:490-553)
+ *                        plus      writeIndex                   db_impl.go:434-454  (Put / Delete / SoftDelete + WriteStat)
  *   bcw_synth_segment    host WAL writer: Wal.WriteRecord wal.go:490-553 over Record.Encode
  *                                  record.go:57-138 (synthetic segments of the benchmark configs)
  *
@@ -652,6 +656,100 @@ int bcw_get_records_async(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p
  * the table untouched) when h_out->payload_cap < payload_need, as bcw_encode_segment does. */
 int bcw_get_records(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p, uint64_t n, const uint8_t* h_keys,
                     const uint64_t* h_key_off, const bcw_get_out* h_out, bcw_get_result* h_result);
+
+/* ---- batched Write (DBImpl.Write, db_impl.go:343-431) ---------------------------------------------------
+ * records given as field arrays -> the bytes writeWal appends to the active WAL (Record.Encode record.go:57-138 per
+ * record, Wal.WriteRecord wal.go:490-553 from wal_pos) -> writeIndex (db_impl.go:434-454: Put / Delete / SoftDelete
+ * with the offsets WriteRecord returned, and each op's WriteStat), without leaving HBM. The group commit
+ * (buildBatchGroup) stays with the caller: one call is one merged batch.
+ *
+ * All or nothing, as writeWal is (ResetBuffer, db_impl.go:465-473, then writeIndex skipped): when any record fails
+ * Record.Encode, or the bytes do not fit wal_cap, no output byte, no rec_off / rec_size entry and no WriteStat entry is
+ * written and the index is untouched; the result names the first failing record, or wal_need.
+ *
+ * Visibility to Get: the caller lets `wal` point into its resident image of the active WAL (wal = d_image + wal_pos)
+ * and, after the call, registers the new length with bcw_walset_put(ws, fid, d_image, wal_end, base_time). A get queued
+ * after that on the same context sees the batch; no other walset call is needed. */
+#define BCW_WR_TOMBSTONE 1 /* Meta.IsTombstone() */
+#define BCW_WR_DELETED 2   /* Record.Deleted (Batch.Delete sets both) */
+#define BCW_WR_ETAG 4      /* Meta.Etag present: etag_size bytes at etags + i * etag_size */
+
+#define BCW_ENC_ERR_BATCH 6 /* bcw_write_records*: a record the table cannot express (a merged key shorter than ns_size,
+                               a payload of 2^32 bytes or more, offsets that descend or leave their array, or
+                               BCW_WR_ETAG without an etags array) at err_record: nothing written */
+
+typedef struct bcw_write_batch { /* n records, batch order = the reference's loop order */
+  uint64_t n;
+  const uint8_t* keys; /* merged keys ns || key (>= ns_size bytes each): key i = keys[key_off[i], key_off[i+1]) */
+  const uint64_t* key_off;
+  uint64_t keys_len;   /* bytes in `keys` (key_off[n] <= keys_len); likewise vals_len, metas_len */
+  const uint8_t* vals;
+  const uint64_t* val_off;
+  uint64_t vals_len;
+  const uint8_t* metas; /* msgpack bytes of Meta.AppMeta, opaque; length 0 when AppMetaSize == 0 (record.go:82-86) */
+  const uint64_t* meta_off;
+  uint64_t metas_len;
+  const uint8_t* etags;   /* n * etag_size bytes, may be NULL when no record has BCW_WR_ETAG */
+  const uint64_t* expire; /* Meta.Expire, 0 = MetaNoExpire */
+  const uint8_t* flags;   /* BCW_WR_* */
+} bcw_write_batch;
+
+typedef struct bcw_write_params {
+  uint64_t fid;       /* the active WAL (manifest.active.Fid()): the fid of every Put */
+  uint64_t base_time; /* active.BaseTime() */
+  uint64_t wal_pos;   /* the active WAL's size before the append, >= 40 */
+  uint32_t ns_size;
+  uint32_t etag_size;
+} bcw_write_params;
+
+/* wal receives the appended bytes: wal[0] is file offset wal_pos (as in bcw_encode_out). Pad bytes are written as
+ * zeros: the buffer need not be clean. rec_off / rec_size (n entries): the reference's locs. found / free_fid /
+ * free_bytes (n entries each; all three or none): the WriteStat columns of bcw_index_apply_stat. */
+typedef struct bcw_write_out {
+  uint8_t* wal;
+  uint64_t wal_cap;
+  uint64_t* rec_off;
+  uint64_t* rec_size;
+  uint8_t* found;
+  uint64_t* free_fid;
+  uint64_t* free_bytes;
+} bcw_write_out;
+
+typedef struct bcw_write_result {
+  uint64_t n_written;  /* records appended and applied: n, or 0 when the batch was rejected */
+  uint64_t wal_end;    /* the active WAL's size after the append (wal_pos when a record failed) */
+  uint64_t wal_need;   /* bytes the batch appends = wal_end - wal_pos */
+  int64_t err_record;  /* the first failing record in batch order, -1 if none */
+  int32_t err_class;   /* BCW_ENC_ERR_NONE, _EXPIRE, _PANIC or _BATCH */
+  int32_t idx_err;     /* 0 or BCW_IDX_ERR_FULL */
+  uint32_t fits;       /* 0: wal_need > wal_cap, nothing was written. Retry with wal_need */
+  uint32_t _pad;
+} bcw_write_result;
+
+/* Async, device-resident: every array of *d_batch_arrays and *d_out is a device pointer (any byte alignment; the
+ * offset arrays 8-byte aligned), the two structs themselves and p are host structs, d_result is a device pointer.
+ * keys_len / vals_len / metas_len are host scalars: the index and the scratch are sized from them without a round
+ * trip. Runs on the index's context stream and does not synchronise (the index grows on the host only when the batch
+ * does not fit its capacity). The offsets must ascend (not checked here). bcw_index_set_limit's bound applies after
+ * the batch, as for bcw_index_apply. */
+int bcw_write_records_async(bcw_index* ix, const bcw_write_params* p, const bcw_write_batch* d_batch_arrays,
+                            const bcw_write_out* d_out, bcw_write_result* d_result);
+/* Synchronous, host in / host out. Returns BCW_E_CAPACITY with the result filled (nothing written, index untouched)
+ * when h_out->wal_cap < wal_need, as bcw_encode_segment does, and BCW_E_INVAL for offsets that do not ascend. The
+ * three *_len fields of h_batch are not read: the offsets give the lengths. */
+int bcw_write_records(bcw_index* ix, const bcw_write_params* p, const bcw_write_batch* h_batch,
+                      const bcw_write_out* h_out, bcw_write_result* h_result);
+/* Host helpers (no device work). bcw_record_encode: Record.Encode (record.go:57-138) of one record into out[0, cap):
+ * returns the payload length, or minus the error class: -BCW_ENC_ERR_EXPIRE / _PANIC / _BATCH as the device reports
+ * them, -BCW_ENC_ERR_TABLE when cap is smaller than the length (nothing written; out == NULL with cap 0 is allowed).
+ * merged_key = ns || key (key_len >= ns_size), flags = BCW_WR_* (the etag is read only with BCW_WR_ETAG). */
+int64_t bcw_record_encode(uint8_t* out, uint64_t cap, const uint8_t* merged_key, uint64_t key_len, const uint8_t* val,
+                          uint64_t val_len, const uint8_t* meta, uint64_t meta_len, const uint8_t* etag,
+                          uint64_t expire, uint32_t flags, uint32_t etag_size, uint64_t base_time, uint32_t ns_size);
+/* Upper bound of wal_need for any batch with these totals: payload headers and varints, the leading pad, one pad
+ * per record and 7 bytes per block touched. */
+uint64_t bcw_write_bound(uint64_t n, uint64_t keys_len, uint64_t vals_len, uint64_t metas_len, uint32_t etag_size,
+                         uint64_t wal_pos);
 
 /* ---- host I/O staging: WAL files <-> HBM through pinned slices ---------------------------------------
  * The reference reads a segment with PreadFull per 32 KiB block (utils.go:32-48, wal_iterator.go:55)
