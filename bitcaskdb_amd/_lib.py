@@ -121,6 +121,11 @@ class IndexResult(C.Structure):
     _fields_ = [("n_in", C.c_uint64), ("n_done", C.c_uint64), ("err_class", C.c_int32), ("_pad", C.c_int32)]
 
 
+class CompactRules(C.Structure):
+    _fields_ = [("mask", C.c_uint32), ("n_prefix", C.c_uint32), ("now", C.c_uint64), ("prefixes", C.c_void_p),
+                ("prefix_off", C.c_void_p)]
+
+
 class RecoverFile(C.Structure):
     _fields_ = [("fid", C.c_uint64), ("wal", C.c_void_p), ("wal_p", DecodeParams), ("hint", C.c_void_p),
                 ("hint_p", DecodeParams)]
@@ -171,6 +176,8 @@ WR_TOMBSTONE, WR_DELETED, WR_ETAG = 1, 2, 4
 IDX_PUT, IDX_DELETE, IDX_SOFT_DELETE = 0, 1, 2
 IDX_FOUND, IDX_NOT_FOUND, IDX_SOFT_DELETED = 0, 1, 2
 IDX_ERR_FULL = 6
+RULE_EXPIRED, RULE_TOMBSTONE, RULE_PREFIX = 1, 2, 4  # bcw_compact_rules.mask
+RULE_MAX_PREFIXES, RULE_MAX_PREFIX_LEN = 64, 64
 RECOVER_NOT_RUN, RECOVER_HINT, RECOVER_HINT_WAL, RECOVER_WAL = 0, 1, 2, 3
 RD_OK, RD_BEYOND, RD_CORRUPTED, RD_CRC, RD_SIZE, RD_TYPE, RD_INCOMPLETE, RD_PANIC = range(8)
 GET_OK, GET_NOT_FOUND, GET_SOFT_DELETED, GET_NO_WAL, GET_READ, GET_RECORD = range(6)
@@ -226,6 +233,8 @@ def _load():
                                                   C.c_uint64, C.c_int, vp]),
         "bcw_compact_filter_async": (C.c_int, [vp, vp, C.POINTER(DecodeParams), C.POINTER(RecordTable), vp,
                                                C.c_uint64, vp, vp]),
+        "bcw_index_set_compact_rules": (C.c_int, [vp, C.POINTER(CompactRules)]),
+        "bcw_index_compact_rule_counts": (C.c_int, [vp, u64p]),
         "bcw_index_export": (C.c_int, [vp, vp, C.c_uint64, u64p, u64p, u64p, u64p, C.c_uint64, u64p, u64p]),
         "bcw_index_export_fids": (C.c_int, [vp, u64p, C.c_uint64, vp, C.c_uint64, u64p, u64p, u64p, u64p,
                                             C.c_uint64, u64p, u64p]),

@@ -890,11 +890,13 @@ int bcw_compact_segment(bcw_ctx* c, bcw_index* ix, const uint8_t* h_src, const b
   if (rc != BCW_OK) return rc;
   rc = ensure_keep(c, c->d_tab.capacity);
   if (rc != BCW_OK) return rc;
-  rc = bcw_compact_filter_async(ix, c->d_seg, &dp, &c->d_tab, c->d_result, src_fid, c->d_keep,
-                                h_filter ? c->d_ires : nullptr);
+  rc = ix_filter_pending(ix, c->d_seg, &dp, &c->d_tab, c->d_result, src_fid, c->d_keep,
+                         h_filter ? c->d_ires : nullptr);
   if (rc != BCW_OK) return rc;
   if (h_filter) HIPCHK(hipMemcpyAsync(h_filter, c->d_ires, sizeof *h_filter, hipMemcpyDeviceToHost, c->cur));
-  return encode_to_host(c, p, h, h_result, dres);
+  rc = encode_to_host(c, p, h, h_result, dres);
+  // the rows the index's rules dropped count once the output is final (not for a call refused with BCW_E_CAPACITY)
+  return rc != BCW_OK ? rc : ix_rule_commit(ix);
 }
 
 int bcw_index_recover_segment(bcw_ctx* c, bcw_index* ix, const uint8_t* h_seg, const bcw_decode_params* p,

@@ -209,6 +209,7 @@ int bcw_compact_wals(bcw_index* ix, bcw_ctx* const* ctxs, uint32_t n_ctx, const 
   // point into the sources, split by fid, each source's slice loaded into a staging index on that context.
   bcw_ctx* const ixc = index_ctx(ix);
   if (!ixc) return BCW_E_INVAL;
+  const bool ruled_on = ix_has_rules(ix);  // the index's compaction filter rules (fixed for the call)
   bool any_remote = false;
   for (uint32_t w = 0; w < n_ctx; ++w) any_remote |= ctxs[w]->device != ixc->device || ctxs[w]->filter_snapshot;
   {
@@ -231,6 +232,7 @@ int bcw_compact_wals(bcw_index* ix, bcw_ctx* const* ctxs, uint32_t n_ctx, const 
   std::condition_variable cv;
   uint64_t turn = 0;  // the source whose encode runs next
   std::vector<uint8_t> copied(n_src, 0);  // sources whose outputs reached the host
+  std::vector<uint64_t> ruled(3 * n_src, 0);  // rows the index's compaction filter rules dropped, per source
   uint64_t wal_pos = dst->wal_pos, hint_pos = dst->hint_pos;
   bool quit = false;
   int err = BCW_OK;
@@ -240,6 +242,7 @@ int bcw_compact_wals(bcw_index* ix, bcw_ctx* const* ctxs, uint32_t n_ctx, const 
     const bool direct = c->device == ixc->device && !c->filter_snapshot;
     Staging stg;
     Entries mine;
+    uint64_t staged[3] = {0, 0, 0};  // the staging index's rule counts so far
     uint64_t* d_cnt = nullptr;  // (direct) the filter's counters
     struct FreeCnt {
       bcw_ctx* c;
@@ -266,7 +269,11 @@ int bcw_compact_wals(bcw_index* ix, bcw_ctx* const* ctxs, uint32_t n_ctx, const 
         DeviceGuard dg(c->device);
         r = dg.ok && hipMalloc(&d_cnt, kIxCounters * sizeof(uint64_t)) == hipSuccess ? BCW_OK : BCW_E_HIP;
       }
-      if (!direct) r = stg.ready(c, m + 16, 64 * m + 4096);
+      if (!direct) {
+        const bool fresh = !stg.ix;
+        r = stg.ready(c, m + 16, 64 * m + 4096);
+        if (r == BCW_OK && fresh && ruled_on) r = ix_forward_rules(stg.ix, ix);
+      }
       if (r == BCW_OK && m) {
         mine.room(m, 0);
         mine.k.clear();
@@ -294,10 +301,22 @@ int bcw_compact_wals(bcw_index* ix, bcw_ctx* const* ctxs, uint32_t n_ctx, const 
           r = direct ? ix_filter_on(ix, c, c->d_seg, &dp, &c->d_tab, c->d_result, S.fid, c->d_keep, d_cnt, c->d_ires)
                      : bcw_compact_filter_async(stg.ix, c->d_seg, &dp, &c->d_tab, c->d_result, S.fid, c->d_keep,
                                                 c->d_ires);
+        if (r == BCW_OK && direct && ruled_on &&
+            hipMemcpyAsync(&ruled[3 * k], d_cnt + kIxRuleCnt, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->cur) !=
+                hipSuccess)
+          r = BCW_E_HIP;
         if (r == BCW_OK && (hipMemcpyAsync(&filt[k], c->d_ires, sizeof filt[k], hipMemcpyDeviceToHost, c->cur) !=
                                 hipSuccess ||
                             hipStreamSynchronize(c->cur) != hipSuccess))
           r = BCW_E_HIP;
+        if (r == BCW_OK && !direct && ruled_on) {  // the staging index counts cumulatively: this source's share
+          uint64_t now[3];
+          r = bcw_index_compact_rule_counts(stg.ix, now);
+          for (int q = 0; r == BCW_OK && q < 3; ++q) {
+            ruled[3 * k + q] = now[q] - staged[q];
+            staged[q] = now[q];
+          }
+        }
       }
       // the encode, in source order: the turn is held until its result (the dst / hint ends) is in; the copies of
       // its outputs to the host then run beside the next source's encode (only the ends chain the sources,
@@ -350,6 +369,8 @@ int bcw_compact_wals(bcw_index* ix, bcw_ctx* const* ctxs, uint32_t n_ctx, const 
   pool.reserve(n_ctx);
   for (uint32_t w = 0; w < n_ctx && w < n_src; ++w) pool.emplace_back(worker, w);
   for (auto& t : pool) t.join();
+  // the rules' counts of the sources whose output is final (a source refused for capacity is filtered again)
+  for (uint64_t k = 0; ruled_on && k < *n_done; ++k) ix_add_rule_counts(ix, &ruled[3 * k]);
   return err;
 }
 

@@ -41,6 +41,7 @@
 
 #include "bcw_internal.h"
 #include "bcw_read_body.h"
+#include "bcw_rules.h"
 
 namespace bcw {
 namespace ix {
@@ -693,6 +694,79 @@ __global__ __launch_bounds__(256) void k_ix_filter(Src s, uint64_t rows, const b
   (void)wave_alloc(&cnt[C_DONE], kp ? 1ull : 0ull);
 }
 
+// k_ix_filter with the index's compaction filter rules (bcw_index_set_compact_rules, bcw_rules.h): the same index
+// check first, then, only for a row that is still kept, the rules in their order -- the two column rules from the
+// table's expire / flags, the prefix rule over the merged key's first 16 B chunks (key_chunk, as the lookup reads
+// them: a namespace or key that straddles fragments takes its slow path) against the prefix table, which the workgroup
+// stages into LDS once. A row counts for the first rule that matches it (one wave-aggregated add per rule and wave).
+// Launched only when rules are set: with none, the filter is k_ix_filter above.
+struct Rules {
+  uint32_t mask, n_prefix, longest;  // n_prefix: 0 unless BCW_RULE_PREFIX is set
+  uint64_t now;
+  const rules::PrefixTable* table;   // device
+  uint64_t* cnt;                     // device: rows dropped by {expired, tombstone, prefix}
+};
+
+__global__ __launch_bounds__(256) void k_ix_filter_rules(Src s, uint64_t rows, const bcw_decode_result* __restrict__ R,
+                                                         uint64_t gen, const Slot* __restrict__ slots, uint64_t mask,
+                                                         const uint8_t* __restrict__ arena, uint64_t src_fid,
+                                                         uint8_t* __restrict__ keep, uint64_t* __restrict__ cnt,
+                                                         Rules ru) {
+  __shared__ __align__(16) rules::PrefixTable pt;
+  {
+    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(ru.table->w);
+    uint4* dst = reinterpret_cast<uint4*>(pt.w);
+    for (uint32_t q = threadIdx.x; q < ru.n_prefix * (rules::kPrefixWords / 4); q += 256) dst[q] = src[q];
+    if (threadIdx.x < ru.n_prefix) pt.len[threadIdx.x] = ru.table->len[threadIdx.x];
+  }
+  __syncthreads();
+  const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
+  const uint32_t fail = table_fail(R, gen, rows);
+  const uint64_t nin = fail ? 0 : delivered_rows(R);
+  if (i == 0) { cnt[C_NIN] = nin; cnt[C_FAIL] = fail; }
+  uint8_t kp = 0;
+  uint32_t hit = rules::kNone;
+  if (i < nin) {
+    const Key k = make_key(s, i);
+    const uint64_t h = key_hash(s, k);
+    const uint64_t j = find_slot(s, k, h, slots, mask, arena);
+    if (j != ~0ull && slots[j].live && slots[j].off != 0)
+      kp = (slots[j].fid == src_fid && slots[j].off == s.t.foff[i] - kHdr) ? 1 : 0;
+    if (kp) {
+      hit = rules::first_match(ru.mask, ru.now, s.t.expire[i], s.t.flags[i], k.len(), pt.w, pt.len, ru.n_prefix,
+                               ru.longest, [&](uint32_t* kw, uint32_t n) {
+#pragma unroll
+                                 for (uint32_t c = 0; c < rules::kKeyChunks; ++c) {
+                                   if (c >= n) break;
+                                   const uint4 v = key_chunk(s, k, c);
+                                   kw[4 * c] = v.x;
+                                   kw[4 * c + 1] = v.y;
+                                   kw[4 * c + 2] = v.z;
+                                   kw[4 * c + 3] = v.w;
+                                 }
+                               });
+      if (hit != rules::kNone) kp = 0;
+    }
+  }
+  if (i < rows) keep[i] = kp;
+  (void)wave_alloc(&cnt[C_DONE], kp ? 1ull : 0ull);
+#pragma unroll
+  for (uint32_t r = rules::kExpired; r <= rules::kPrefix; ++r) {
+    const uint64_t b = __ballot(hit == r);
+    if ((threadIdx.x & 63u) == 0 && b)
+      atomicAdd(reinterpret_cast<unsigned long long*>(&ru.cnt[r - 1]), (unsigned long long)__popcll(b));
+  }
+}
+
+// the rule counts of a synchronous compaction whose output is final join the cumulative ones (rule counters:
+// [0, 3) cumulative, [3, 6) the compaction in progress)
+__global__ void k_ix_rule_commit(uint64_t* __restrict__ rc) {
+  for (int r = 0; r < 3; ++r) {
+    rc[r] += rc[3 + r];
+    rc[3 + r] = 0;
+  }
+}
+
 __global__ void k_ix_result(const uint64_t* __restrict__ cnt, bcw_index_result* __restrict__ r) {
   bcw_index_result o{};
   o.n_in = cnt[C_NIN];
@@ -966,6 +1040,17 @@ struct bcw_index {
   void* stage = nullptr;
   uint64_t stage_cap = 0;
   bcw_index_result* d_res = nullptr;
+  // compaction filter rules (bcw_index_set_compact_rules): the host copy (mask 0: none; the prefix arrays point into
+  // the two vectors), the packed prefix table and the counters on the device (allocated with the first rules: three
+  // cumulative words, then the three of a synchronous compaction in progress, k_ix_rule_commit), and the counts
+  // bcw_compact_wals' workers took per source, added on the host for the sources whose output is final
+  bcw_compact_rules rules{};
+  std::vector<uint8_t> rule_bytes;
+  std::vector<uint32_t> rule_off;
+  uint32_t rule_longest = 0;
+  rules::PrefixTable* d_rule_tab = nullptr;
+  uint64_t* d_rule_cnt = nullptr;
+  uint64_t rule_host[3] = {0, 0, 0};
 };
 
 namespace bcw {
@@ -1162,6 +1247,26 @@ Src table_src(bcw_ctx* c, const uint8_t* d_seg, const bcw_decode_params* p, cons
   return s;
 }
 
+// doFilter of every row of a decoded table on stream st, counters in cnt: with no rules set the filter without
+// rules (k_ix_filter, as it always was), else the rules variant, which counts the rows each rule drops into
+// rule_cnt (three device words). A table the rules cannot read is refused.
+int ix_launch_filter(bcw_index* x, const Src& s, uint64_t rows, const bcw_decode_result* d_result, uint64_t gen,
+                     uint64_t src_fid, uint8_t* d_keep, uint64_t* cnt, uint64_t* rule_cnt, hipStream_t st) {
+  if (!rows) return BCW_OK;
+  const uint32_t grid = (uint32_t)((rows + 255) / 256);
+  if (!x->rules.mask) {
+    k_ix_filter<<<grid, 256, 0, st>>>(s, rows, d_result, gen, x->slots, x->cap - 1, x->arena, src_fid, d_keep, cnt);
+    return BCW_OK;
+  }
+  if (!s.t.expire || !s.t.flags) return BCW_E_INVAL;
+  const bool pfx = (x->rules.mask & BCW_RULE_PREFIX) != 0;
+  const Rules ru{x->rules.mask, pfx ? x->rules.n_prefix : 0u, pfx ? x->rule_longest : 0u, x->rules.now, x->d_rule_tab,
+                 rule_cnt};
+  k_ix_filter_rules<<<grid, 256, 0, st>>>(s, rows, d_result, gen, x->slots, x->cap - 1, x->arena, src_fid, d_keep, cnt,
+                                          ru);
+  return BCW_OK;
+}
+
 }  // namespace
 
 namespace bcw {
@@ -1266,7 +1371,8 @@ namespace bcw {
 int ix_filter_on(bcw_index* x, bcw_ctx* c, const uint8_t* d_seg, const bcw_decode_params* p,
                  const bcw_record_table* d_table, const bcw_decode_result* d_result, uint64_t src_fid, uint8_t* d_keep,
                  uint64_t* d_cnt, bcw_index_result* d_out) {
-  static_assert(C_NUM <= kIxCounters, "the per-call counters hold every index counter");
+  static_assert(C_NUM <= kIxRuleCnt && kIxRuleCnt + 3 <= kIxCounters,
+                "the per-call counters hold every index counter and the three rule counts");
   if (!x || !c || !p || !d_table || !d_result || !d_keep || !d_cnt || p->mode != BCW_MODE_RECORD ||
       c->device != x->ctx->device)
     return BCW_E_INVAL;
@@ -1280,12 +1386,65 @@ int ix_filter_on(bcw_index* x, bcw_ctx* c, const uint8_t* d_seg, const bcw_decod
   // the index's counters (its overflow flag included), then this call's own zeroed
   (void)hipMemcpyAsync(d_cnt, x->cnt, C_NUM * sizeof(uint64_t), hipMemcpyDeviceToDevice, st);
   (void)hipMemsetAsync(d_cnt + C_NIN, 0, 3 * sizeof(uint64_t), st);
+  if (x->rules.mask) (void)hipMemsetAsync(d_cnt + kIxRuleCnt, 0, 3 * sizeof(uint64_t), st);  // this call's counts
   const Src s = table_src(c, d_seg, p, d_table, SRC_RECORD);
-  if (rows)
-    k_ix_filter<<<(uint32_t)((rows + 255) / 256), 256, 0, st>>>(s, rows, d_result, c->frag_gen, x->slots, x->cap - 1,
-                                                                 x->arena, src_fid, d_keep, d_cnt);
+  const int rc = ix_launch_filter(x, s, rows, d_result, c->frag_gen, src_fid, d_keep, d_cnt, d_cnt + kIxRuleCnt, st);
+  if (rc != BCW_OK) return rc;
   if (d_out) k_ix_result<<<1, 1, 0, st>>>(d_cnt, d_out);
   return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
+}
+
+bool ix_has_rules(const bcw_index* x) { return x->rules.mask != 0; }
+
+int ix_forward_rules(bcw_index* to, const bcw_index* from) {
+  return from->rules.mask ? bcw_index_set_compact_rules(to, &from->rules) : BCW_OK;
+}
+
+void ix_add_rule_counts(bcw_index* to, const uint64_t c[3]) {
+  for (int r = 0; r < 3; ++r) to->rule_host[r] += c[r];
+}
+
+int ix_rule_commit(bcw_index* x) {
+  if (!x->rules.mask) return BCW_OK;
+  DeviceGuard dg(x->ctx->device);
+  if (!dg.ok) return BCW_E_HIP;
+  k_ix_rule_commit<<<1, 1, 0, x->ctx->cur>>>(x->d_rule_cnt);
+  return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
+}
+}  // namespace bcw
+
+namespace {
+// bcw_compact_filter_async; pending: the rows the rules drop are counted apart, for ix_rule_commit
+int ix_filter_own(bcw_index* x, const uint8_t* d_seg, const bcw_decode_params* p, const bcw_record_table* d_table,
+                  const bcw_decode_result* d_result, uint64_t src_fid, uint8_t* d_keep, bcw_index_result* d_out,
+                  bool pending) {
+  if (!x || !p || !d_table || !d_result || !d_keep || p->mode != BCW_MODE_RECORD) return BCW_E_INVAL;
+  bcw_ctx* c = x->ctx;
+  if (!c->s.frags || !d_table->foff || !d_table->key_len || !d_table->first_frag || !d_table->emit_frag ||
+      !d_table->hdr_size)
+    return BCW_E_INVAL;
+  DeviceGuard dg(c->device);
+  if (!dg.ok) return BCW_E_HIP;
+  const uint64_t rows = d_table->capacity;
+  hipStream_t st = c->cur;
+  (void)hipMemsetAsync(x->cnt + C_NIN, 0, 3 * sizeof(uint64_t), st);
+  uint64_t* rule_cnt = x->d_rule_cnt;
+  if (pending && x->rules.mask) {
+    rule_cnt += 3;
+    (void)hipMemsetAsync(rule_cnt, 0, 3 * sizeof(uint64_t), st);
+  }
+  const Src s = table_src(c, d_seg, p, d_table, SRC_RECORD);
+  const int rc = ix_launch_filter(x, s, rows, d_result, c->frag_gen, src_fid, d_keep, x->cnt, rule_cnt, st);
+  if (rc != BCW_OK) return rc;
+  if (d_out) k_ix_result<<<1, 1, 0, st>>>(x->cnt, d_out);
+  return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
+}
+}  // namespace
+
+namespace bcw {
+int ix_filter_pending(bcw_index* x, const uint8_t* d_seg, const bcw_decode_params* p, const bcw_record_table* d_table,
+                      const bcw_decode_result* d_result, uint64_t src_fid, uint8_t* d_keep, bcw_index_result* d_out) {
+  return ix_filter_own(x, d_seg, p, d_table, d_result, src_fid, d_keep, d_out, true);
 }
 }  // namespace bcw
 
@@ -1315,7 +1474,8 @@ int bcw_index_destroy(bcw_index* x) {
   if (!x) return BCW_E_INVAL;
   DeviceGuard dg(x->ctx->device);
   (void)hipStreamSynchronize(x->ctx->cur);
-  void* ptrs[] = {x->slots, x->arena, x->cnt, x->op_kref, x->op_hash, x->op_slot, x->stage, x->d_res};
+  void* ptrs[] = {x->slots, x->arena, x->cnt, x->op_kref, x->op_hash, x->op_slot, x->stage, x->d_res,
+                  x->d_rule_tab, x->d_rule_cnt};
   for (void* q : ptrs) (void)hipFree(q);
   delete x;
   return BCW_OK;
@@ -1563,22 +1723,68 @@ int bcw_index_put_decoded_async(bcw_index* x, const uint8_t* d_seg, const bcw_de
 int bcw_compact_filter_async(bcw_index* x, const uint8_t* d_seg, const bcw_decode_params* p,
                              const bcw_record_table* d_table, const bcw_decode_result* d_result, uint64_t src_fid,
                              uint8_t* d_keep, bcw_index_result* d_out) {
-  if (!x || !p || !d_table || !d_result || !d_keep || p->mode != BCW_MODE_RECORD) return BCW_E_INVAL;
-  bcw_ctx* c = x->ctx;
-  if (!c->s.frags || !d_table->foff || !d_table->key_len || !d_table->first_frag || !d_table->emit_frag ||
-      !d_table->hdr_size)
-    return BCW_E_INVAL;
-  DeviceGuard dg(c->device);
+  return ix_filter_own(x, d_seg, p, d_table, d_result, src_fid, d_keep, d_out, false);
+}
+
+int bcw_index_set_compact_rules(bcw_index* x, const bcw_compact_rules* r) {
+  if (!x || rules::validate(r) != BCW_OK) return BCW_E_INVAL;
+  DeviceGuard dg(x->ctx->device);
   if (!dg.ok) return BCW_E_HIP;
-  const uint64_t rows = d_table->capacity;
-  hipStream_t st = c->cur;
-  (void)hipMemsetAsync(x->cnt + C_NIN, 0, 3 * sizeof(uint64_t), st);
-  const Src s = table_src(c, d_seg, p, d_table, SRC_RECORD);
-  if (rows)
-    k_ix_filter<<<(uint32_t)((rows + 255) / 256), 256, 0, st>>>(s, rows, d_result, c->frag_gen, x->slots, x->cap - 1,
-                                                                 x->arena, src_fid, d_keep, x->cnt);
-  if (d_out) k_ix_result<<<1, 1, 0, st>>>(x->cnt, d_out);
-  return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
+  hipStream_t st = x->ctx->cur;
+  const bool on = r && r->mask;
+  if (on && !x->d_rule_tab) {
+    rules::PrefixTable* t = nullptr;
+    uint64_t* cnt = nullptr;
+    if (hipMalloc(&t, sizeof *t) != hipSuccess || hipMalloc(&cnt, 6 * sizeof(uint64_t)) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(t);
+      return BCW_E_NOMEM;
+    }
+    x->d_rule_tab = t;
+    x->d_rule_cnt = cnt;
+  }
+  // the copy of the caller's arrays, made before anything of the index changes
+  std::vector<uint8_t> bytes;
+  std::vector<uint32_t> off(1, 0u);
+  rules::PrefixTable tab;
+  uint32_t longest = 0;
+  if (on) {
+    for (uint32_t i = 0; i < r->n_prefix; ++i) {
+      bytes.insert(bytes.end(), r->prefixes + r->prefix_off[i], r->prefixes + r->prefix_off[i + 1]);
+      off.push_back((uint32_t)bytes.size());
+    }
+    longest = rules::pack(*r, &tab);
+    // ordered on the stream after the filters queued so far; the sync below keeps `tab` alive for the copy
+    if (hipMemcpyAsync(x->d_rule_tab, &tab, sizeof tab, hipMemcpyHostToDevice, st) != hipSuccess) return BCW_E_HIP;
+  }
+  if (x->d_rule_cnt && hipMemsetAsync(x->d_rule_cnt, 0, 6 * sizeof(uint64_t), st) != hipSuccess) return BCW_E_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess) return BCW_E_HIP;
+  x->rule_bytes.swap(bytes);
+  x->rule_off.swap(off);
+  x->rules = bcw_compact_rules{};
+  if (on) {
+    x->rules.mask = r->mask;
+    x->rules.n_prefix = r->n_prefix;
+    x->rules.now = r->now;
+    x->rules.prefixes = x->rule_bytes.data();
+    x->rules.prefix_off = x->rule_off.data();
+  }
+  x->rule_longest = longest;
+  x->rule_host[0] = x->rule_host[1] = x->rule_host[2] = 0;
+  return BCW_OK;
+}
+
+int bcw_index_compact_rule_counts(bcw_index* x, uint64_t out[3]) {
+  if (!x || !out) return BCW_E_INVAL;
+  DeviceGuard dg(x->ctx->device);
+  if (!dg.ok) return BCW_E_HIP;
+  hipStream_t st = x->ctx->cur;
+  uint64_t c[3] = {0, 0, 0};
+  if (x->d_rule_cnt && hipMemcpyAsync(c, x->d_rule_cnt, sizeof c, hipMemcpyDeviceToHost, st) != hipSuccess)
+    return BCW_E_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess) return BCW_E_HIP;
+  for (int r = 0; r < 3; ++r) out[r] = c[r] + x->rule_host[r];
+  return BCW_OK;
 }
 
 int bcw_index_export(bcw_index* x, uint8_t* h_keys, uint64_t keys_cap, uint64_t* h_key_off, uint64_t* h_fid,

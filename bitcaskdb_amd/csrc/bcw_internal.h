@@ -218,9 +218,23 @@ bcw_ctx* index_ctx(const bcw_index* ix);
 // counters in d_cnt (kIxCounters words of c's device): another context on the index's device filters against the
 // index itself, read-only, while no call modifies it (bcw_compact_wals).
 constexpr int kIxCounters = 16;
+constexpr int kIxRuleCnt = 13;  // d_cnt[kIxRuleCnt, +3): the rows the index's compaction filter rules dropped in the call
 int ix_filter_on(bcw_index* x, bcw_ctx* c, const uint8_t* d_seg, const bcw_decode_params* p,
                  const bcw_record_table* d_table, const bcw_decode_result* d_result, uint64_t src_fid, uint8_t* d_keep,
                  uint64_t* d_cnt, bcw_index_result* d_out);
+// The compaction filter rules' counters across the synchronous compactions. bcw_compact_filter_async counts into the
+// index's cumulative counters; a compaction that may be refused for capacity and run again counts a source only when
+// its output is final. bcw_compact_segment: ix_filter_pending (bcw_compact_filter_async with the counts held apart),
+// then ix_rule_commit once the encode's outputs are out. bcw_compact_wals: ix_filter_on leaves the call's counts in
+// d_cnt[kIxRuleCnt, +3); a staging index gets the main index's rules (ix_forward_rules) and counts for itself; the
+// caller adds the counts of the final sources on the host (ix_add_rule_counts). Without rules (ix_has_rules) none of
+// this runs: no launch, copy or synchronisation is added to a compaction.
+int ix_filter_pending(bcw_index* x, const uint8_t* d_seg, const bcw_decode_params* p, const bcw_record_table* d_table,
+                      const bcw_decode_result* d_result, uint64_t src_fid, uint8_t* d_keep, bcw_index_result* d_out);
+int ix_rule_commit(bcw_index* x);
+bool ix_has_rules(const bcw_index* x);
+int ix_forward_rules(bcw_index* to, const bcw_index* from);
+void ix_add_rule_counts(bcw_index* to, const uint64_t c[3]);
 
 // The lookup step of a batched Get (bcw_get.hip drives it; the kernel lives with the index, bcw_index.hip): one lane
 // per key. Writes get_status / rd_status / fid / off / size, the request's slot size into out.pay_off (the scan

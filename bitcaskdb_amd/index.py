@@ -269,6 +269,44 @@ class Index:
         if rc != 0:
             raise RuntimeError(f"bcw_index_compact: {L.lib.bcw_strerror(rc).decode()}")
 
+    # ---- compaction filter rules (Options.CompactionFilter as predicates, doFilter compaction.go:339-345) ----
+    def set_compact_rules(self, now: int | None = None, drop_expired: bool = False, drop_tombstones: bool = False,
+                          prefixes=()):
+        """the rules every device doFilter against this index applies to the rows that passed the index check
+        (bcw_index_set_compact_rules): drop records expired by `now` (Unix seconds; default: the wall clock),
+        tombstones, and records whose merged key ns || key starts with one of `prefixes` (at most 64, of 1..64 bytes
+        each). Resets the rule counters. With nothing to drop this clears the rules. ValueError for rules the library
+        refuses; the previous rules then stay in force."""
+        prefixes = [bytes(p) for p in prefixes]
+        mask = (L.RULE_EXPIRED if drop_expired else 0) | (L.RULE_TOMBSTONE if drop_tombstones else 0) | \
+            (L.RULE_PREFIX if prefixes else 0)
+        if now is None:
+            import time
+            now = int(time.time())
+        flat, off = _pack(prefixes)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        r = L.CompactRules(mask, len(prefixes), int(now), flat.ctypes.data, off.ctypes.data)
+        rc = L.lib.bcw_index_set_compact_rules(self._h, C.byref(r))
+        if rc == L.E_INVAL:
+            raise ValueError("bcw_index_set_compact_rules: invalid rules")
+        if rc != 0:
+            raise RuntimeError(f"bcw_index_set_compact_rules: {L.lib.bcw_strerror(rc).decode()}")
+
+    def clear_compact_rules(self):
+        """no rules: doFilter is the index check alone again; the rule counters read zero"""
+        rc = L.lib.bcw_index_set_compact_rules(self._h, None)
+        if rc != 0:
+            raise RuntimeError(f"bcw_index_set_compact_rules: {L.lib.bcw_strerror(rc).decode()}")
+
+    def compact_rule_counts(self) -> dict:
+        """rows each rule dropped since the rules were last set ({"expired", "tombstone", "prefix"}): a row counts
+        for the first rule, in that order, that matches it; rows the index check dropped are not counted"""
+        c = (C.c_uint64 * 3)()
+        rc = L.lib.bcw_index_compact_rule_counts(self._h, c)
+        if rc != 0:
+            raise RuntimeError(f"bcw_index_compact_rule_counts: {L.lib.bcw_strerror(rc).decode()}")
+        return {"expired": int(c[0]), "tombstone": int(c[1]), "prefix": int(c[2])}
+
     def export(self, fids=None) -> dict:
         """every live entry: {merged key: (fid, off, size)}; fids: only entries whose value fid is one of them
         (bcw_index_export_fids)"""

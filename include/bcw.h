@@ -447,12 +447,52 @@ int bcw_index_put_decoded_async(bcw_index* ix, const uint8_t* d_seg, const bcw_d
                                 int use_record_fid, bcw_index_result* d_out);
 /* compactOneWal's doFilter (compaction.go:329-348) on the device, for every delivered row of a decoded
  * data WAL: d_keep[i] = 1 when Index.Get(ns, key) succeeds and still points at (src_fid, foff - 7)
- * (compaction.go:302), else 0 (rows not delivered: 0). The user CompactionFilter, when configured, stays a
- * host callback over the kept rows. d_keep has the table's capacity; it feeds bcw_encode_segment_async
+ * (compaction.go:302), else 0 (rows not delivered: 0). A user CompactionFilter (compaction.go:339-345) that is one
+ * of the rule predicates below -- expired by now, tombstone, namespace / key prefix -- is set on the index
+ * (bcw_index_set_compact_rules) and evaluated here, in the same pass, for the rows that passed the index check: a
+ * row a rule matches gets 0 as well, and n_done counts the rows kept after the rules. Any other CompactionFilter
+ * stays a host callback over the kept rows. d_keep has the table's capacity; it feeds bcw_encode_segment_async
  * directly (decode -> filter -> encode without leaving HBM). */
 int bcw_compact_filter_async(bcw_index* ix, const uint8_t* d_seg, const bcw_decode_params* p,
                              const bcw_record_table* d_table, const bcw_decode_result* d_result, uint64_t src_fid,
                              uint8_t* d_keep, bcw_index_result* d_out);
+/* Compaction filter rules: Options.CompactionFilter (doFilter, compaction.go:339-345) for the filters that are pure
+ * predicates over fields the decode already has. Like the callback they belong to the database, so they are stored
+ * with the index; every device doFilter (bcw_compact_filter_async, bcw_compact_segment, bcw_compact_wals on both of
+ * its filter paths) applies them to the rows that passed the index check, and a match drops the row. The rules are
+ * tried in this order, and a dropped row is counted for the first one that matches:
+ *   BCW_RULE_EXPIRED    expire != 0 && expire <= now (expire: the record table's column, baseTime included; the
+ *                       only way a record with Meta.Expire is ever removed: DBImpl.Get does not look at it)
+ *   BCW_RULE_TOMBSTONE  the record's flag byte has tombstoneFieldBit (bit 2, record.go:44-48)
+ *   BCW_RULE_PREFIX     MergedKey(ns, key) = ns || key (utils.go:133-139) starts with one of the prefixes: shorter
+ *                       than ns_size a namespace prefix, ns_size bytes a whole namespace, longer a key prefix inside
+ *                       one namespace; a prefix longer than the merged key never matches
+ * The caps are part of the design: 64 prefixes of 64 bytes are 4 KiB, staged once per workgroup. */
+#define BCW_RULE_EXPIRED 1u
+#define BCW_RULE_TOMBSTONE 2u
+#define BCW_RULE_PREFIX 4u
+#define BCW_RULE_MAX_PREFIXES 64u
+#define BCW_RULE_MAX_PREFIX_LEN 64u
+typedef struct bcw_compact_rules {
+  uint32_t mask;              /* BCW_RULE_* */
+  uint32_t n_prefix;          /* <= BCW_RULE_MAX_PREFIXES */
+  uint64_t now;               /* Unix seconds, for BCW_RULE_EXPIRED */
+  const uint8_t* prefixes;    /* host: prefix i = prefixes[prefix_off[i], prefix_off[i+1]), 1..64 bytes each */
+  const uint32_t* prefix_off; /* host, n_prefix + 1 entries */
+} bcw_compact_rules;
+/* Set the rules (copied: the arrays need not outlive the call) and reset the three counters. NULL or mask == 0
+ * clears the rules: the filter is then the one without rules, launch for launch. Ordered on the index's context
+ * stream against filters queued before and after it; like every index call, one caller at a time. BCW_E_INVAL,
+ * with the previous rules and counters untouched, for an unknown mask bit, n_prefix > 64, an empty prefix or one
+ * longer than 64 bytes, offsets that descend, or n_prefix > 0 with a NULL array. BCW_RULE_PREFIX with n_prefix == 0
+ * is accepted and matches nothing. */
+int bcw_index_set_compact_rules(bcw_index* ix, const bcw_compact_rules* r);
+/* Rows each rule dropped since the rules were last set: out = {expired, tombstone, prefix}. A row counts for the
+ * first rule that matches it; a row the index check dropped is never counted (the reference's callback would not
+ * have been asked about it). bcw_compact_filter_async counts when it runs; bcw_compact_segment and bcw_compact_wals
+ * count a source once its output is final, so a call refused with BCW_E_CAPACITY and made again counts its rows
+ * once. Synchronises the index's stream. */
+int bcw_index_compact_rule_counts(bcw_index* ix, uint64_t out[3]);
 /* Every live entry (merged key, fid, off, size), in no particular order, into host arrays (h_key_off has
  * entries_cap + 1 entries). Returns BCW_E_CAPACITY when too small (*n_out / *key_bytes tell the sizes). */
 int bcw_index_export(bcw_index* ix, uint8_t* h_keys, uint64_t keys_cap, uint64_t* h_key_off, uint64_t* h_fid,
