@@ -4,7 +4,8 @@ The product is libbcw.so (C-ABI in include/bcw.h, HIP kernels for gfx950 in csrc
 is the Python host mirror of the reference interface (wal.py: the WAL iterators, compaction re-encode,
 hint rebuild; index.py: the device-resident index, its rebuild from hint / data WALs, the device
 compaction filter and the batched Get by key against resident WALs; write.py: the batched Write into the
-active WAL's resident image) and its ctypes binding (_lib.py).
+active WAL's resident image; usage.py: live and freed bytes per WAL file for the compaction picker) and its ctypes
+binding (_lib.py).
 """
 from . import _lib
 from .wal import (Context, Decoded, ErrCorruptedHintRecord, ErrInvalidData, ErrShortFile, ErrWalMismatchBlockSize,
@@ -15,6 +16,7 @@ from .staging import Stage
 from .index import (ErrKeyNotFound, ErrKeySoftDeleted, GetBatch, Index, WalSet, compact_one_wal_filtered, merged_key,
                     murmur3_sum64, recover_from_wals)
 from .write import ActiveWal, WriteBatch
+from .usage import FidUsage, PickerWalInfo, default_compaction_picker, wal_garbage
 
 __all__ = ["Context", "Decoded", "ErrCorruptedHintRecord", "ErrInvalidData", "ErrShortFile",
            "ErrWalMismatchBlockSize", "ErrWalMismatchCRC", "ErrWalMismatchMagic", "ErrWalUnknownRecordType",
@@ -22,4 +24,4 @@ __all__ = ["Context", "Decoded", "ErrCorruptedHintRecord", "ErrInvalidData", "Er
            "iterate_hint", "iterate_record", "load_wal", "_lib", "WalFile", "compact_one_wal",
            "new_hint_by_wal", "ErrKeyNotFound", "ErrKeySoftDeleted", "Index", "compact_one_wal_filtered",
            "merged_key", "murmur3_sum64", "recover_from_wals", "Stage", "WalSet", "GetBatch", "ActiveWal",
-           "WriteBatch"]
+           "WriteBatch", "FidUsage", "PickerWalInfo", "default_compaction_picker", "wal_garbage"]

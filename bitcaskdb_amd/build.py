@@ -7,7 +7,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRCS = [os.path.join(HERE, "csrc", f) for f in ("bcw_api.cpp", "bcw_decode.hip", "bcw_encode.hip", "bcw_fanout.cpp", "bcw_get.hip", "bcw_index.hip", "bcw_io.cpp", "bcw_put.hip", "bcw_read.hip")]
+SRCS = [os.path.join(HERE, "csrc", f) for f in ("bcw_api.cpp", "bcw_decode.hip", "bcw_encode.hip", "bcw_fanout.cpp", "bcw_get.hip", "bcw_index.hip", "bcw_io.cpp", "bcw_put.hip", "bcw_read.hip", "bcw_usage.hip")]
 OUT = os.path.join(HERE, "libbcw.so")
 ARCH = os.environ.get("BCW_OFFLOAD_ARCH", "gfx950")
 
@@ -32,7 +32,7 @@ def build(force: bool = False, verbose: bool = True, sanitize: bool = False) -> 
     tools/sanitize_cpu.sh"""
     out = os.path.join(HERE, "libbcw_asan.so") if sanitize else OUT
     deps = SRCS + [os.path.join(HERE, "csrc", h) for h in ("bcw_internal.h", "bcw_parse.h", "bcw_read_body.h",
-                                                          "bcw_walset.h", "bcw_rules.h")] + \
+                                                          "bcw_walset.h", "bcw_rules.h", "bcw_usage.h")] + \
         [os.path.join(ROOT, "include", "bcw.h")]
     if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps):
         return out

@@ -379,6 +379,7 @@ int bcw_ctx_destroy(bcw_ctx* c) {
   (void)hipFree(c->d_tab_mem);
   (void)hipFree(c->d_result);
   (void)hipFree(c->d_ires);
+  (void)hipFree(c->usage);
   for (auto& m : c->prof.marks) { (void)hipEventDestroy(m.a); (void)hipEventDestroy(m.b); }
   for (auto e : c->prof.pool) (void)hipEventDestroy(e);
   if (c->own) (void)hipStreamDestroy(c->own);
@@ -502,7 +503,8 @@ int bcw_decode_fragments_async(bcw_ctx* c, const bcw_frag_table* d_frags) {
 static const char* kKernelNames[K_NUM] = {"k_chase", "k_crc", "(retired)", "k_enc_prep", "k_enc_scan", "k_events",
                                           "k_write", "k_hint_layout", "k_events_hint", "k_get_lookup",
                                           "k_get_scan", "k_get_read", "k_put_prep", "k_put_layout", "k_put_frags",
-                                          "k_put_write", "k_put_index"};
+                                          "k_put_write", "k_put_index", "k_ix_usage", "k_usage_rows",
+                                          "k_usage_final", "k_ix_live_bytes"};
 
 int bcw_ctx_reserve_fragments(bcw_ctx* c, uint64_t n) {
   if (!c || n >= 0xfffffff0ull) return BCW_E_INVAL;

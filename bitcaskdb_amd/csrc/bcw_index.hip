@@ -42,6 +42,7 @@
 #include "bcw_internal.h"
 #include "bcw_read_body.h"
 #include "bcw_rules.h"
+#include "bcw_usage.h"
 
 namespace bcw {
 namespace ix {
@@ -1015,6 +1016,58 @@ __global__ __launch_bounds__(1024) void k_ix_evict(Slot* __restrict__ slots, uin
   }
 }
 
+// ---- live usage per fid (bcw_index_fid_usage*, bcw_usage.h): one read-only pass over the slot table ----------
+// A workgroup takes 256 slots per round: their 16 KiB go through LDS as 1024 contiguous 16 B loads (every lane's load
+// next to its neighbour's; a slot's four chunks land rotated by its index so that the lanes' 16 B reads of one field
+// pair spread over all banks), then each lane reads {fid}, {off, size}, {live} of its own slot. A slot is counted iff
+// live and off >= 40; its span is WalRecordSize in closed form (the size is not trusted). Rows go to the workgroup's
+// accumulator; soft-deleted (live, off == 0) and invalid (live, 0 < off < 40) slots are only counted.
+constexpr uint32_t kUsageSlots = usage::kThreads;  // slots per workgroup round
+__device__ __forceinline__ uint32_t usage_chunk_pos(uint32_t slot, uint32_t q) { return slot * 4 + (q ^ ((slot >> 2) & 3u)); }
+
+__global__ __launch_bounds__(usage::kThreads) void k_ix_usage(const Slot* __restrict__ slots, uint64_t cap,
+                                                              uint64_t* __restrict__ scratch) {
+  __shared__ usage::Accum acc;
+  __shared__ uint4 stage[kUsageSlots * 4];
+  acc.init();
+  const usage::Table g = usage::table_of(scratch);
+  const uint32_t tid = threadIdx.x;
+  uint64_t n_soft = 0, n_inv = 0;
+  for (uint64_t base = (uint64_t)blockIdx.x * kUsageSlots; base < cap; base += (uint64_t)gridDim.x * kUsageSlots) {
+    const uint64_t left = cap - base;
+    const uint32_t nslots = left < kUsageSlots ? (uint32_t)left : kUsageSlots;
+    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(slots + base);
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+      const uint32_t j = k * usage::kThreads + tid;  // chunk j of the round: slot j / 4, 16 B part j % 4
+      if (j < nslots * 4) stage[usage_chunk_pos(j >> 2, j & 3u)] = src[j];
+    }
+    __syncthreads();
+    const bool valid = tid < nslots;
+    const uint4 hf = stage[usage_chunk_pos(tid, 1)], os = stage[usage_chunk_pos(tid, 2)],
+                lp = stage[usage_chunk_pos(tid, 3)];
+    __syncthreads();  // the next round overwrites the staging buffer
+    const uint64_t fid = (uint64_t)hf.z | ((uint64_t)hf.w << 32);
+    const uint64_t off = (uint64_t)os.x | ((uint64_t)os.y << 32), size = (uint64_t)os.z | ((uint64_t)os.w << 32);
+    const bool live = valid && (lp.x | lp.y) != 0;
+    const bool counted = live && off >= BCW_SUPER_BLOCK_SIZE;
+    n_soft += (live && off == 0) ? 1 : 0;
+    n_inv += (live && off != 0 && off < BCW_SUPER_BLOCK_SIZE) ? 1 : 0;
+    const uint64_t span = counted ? usage::wal_record_size_closed(off, size) : 0;
+    acc.add(g, counted, fid, true, size, span);
+  }
+  acc.flush(g);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    n_soft += __shfl_xor(n_soft, d, 64);
+    n_inv += __shfl_xor(n_inv, d, 64);
+  }
+  if ((tid & 63u) == 0) {
+    if (n_soft) atomicAdd(&g.aux[usage::A_SOFT], (unsigned long long)n_soft);
+    if (n_inv) atomicAdd(&g.aux[usage::A_INVALID], (unsigned long long)n_inv);
+  }
+}
+
 }  // namespace ix
 }  // namespace bcw
 
@@ -1528,9 +1581,13 @@ int bcw_index_compact(bcw_index* x, int shrink) {
   hipStream_t st = x->ctx->cur;
   uint64_t ncap = x->cap, narena = x->arena_cap;
   if (shrink && hipMemsetAsync(x->cnt + C_R_ARENA, 0, sizeof(uint64_t), st) != hipSuccess) return BCW_E_HIP;
-  if (shrink)
+  if (shrink) {
+    hipEvent_t ev = nullptr;
+    x->ctx->prof.begin(K_IX_LIVE_BYTES, st, ev);
     k_ix_live_bytes<<<(uint32_t)((x->cap + 255) / 256), 256, 0, st>>>(x->slots, x->cap, x->arena, x->arena_cap,
                                                                       x->cnt + C_R_ARENA);
+    x->ctx->prof.end(K_IX_LIVE_BYTES, st, ev);
+  }
   uint64_t c[C_NUM];
   const int rc = hipGetLastError() == hipSuccess ? ix_sync_counters(x, c) : BCW_E_HIP;
   if (rc != BCW_OK) return rc;
@@ -1813,6 +1870,53 @@ int bcw_index_export_fids(bcw_index* x, const uint64_t* h_fids, uint64_t n_fids,
   sink.size = h_size;
   const int rc = ix_export(x, h_fids, n_fids, sink, n_out, key_bytes);
   if (rc == BCW_OK && *n_out == 0 && h_key_off) h_key_off[0] = 0;
+  return rc;
+}
+
+int bcw_index_fid_usage_async(bcw_index* x, bcw_fid_usage* d_rows, uint32_t cap, bcw_usage_result* d_res) {
+  if (!x || !d_res || (cap && !d_rows)) return BCW_E_INVAL;
+  bcw_ctx* c = x->ctx;
+  DeviceGuard dg(c->device);
+  if (!dg.ok) return BCW_E_HIP;
+  hipStream_t st = c->cur;
+  uint64_t* scratch = nullptr;
+  const int rc = usage_begin(c, st, &scratch);
+  if (rc != BCW_OK) return rc;
+  if (x->slots && x->cap) {  // the buffers as they are now: a batch queued before this call has already grown them
+    const uint64_t wgs = (x->cap + kUsageSlots - 1) / kUsageSlots;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(wgs, (uint64_t)c->num_cus * 8);
+    hipEvent_t ev = nullptr;
+    c->prof.begin(K_USAGE_INDEX, st, ev);
+    k_ix_usage<<<grid, usage::kThreads, 0, st>>>(x->slots, x->cap, scratch);
+    c->prof.end(K_USAGE_INDEX, st, ev);
+    if (hipGetLastError() != hipSuccess) return BCW_E_HIP;
+  }
+  return usage_finish(c, st, d_rows, cap, d_res, 1);
+}
+
+int bcw_index_fid_usage(bcw_index* x, bcw_fid_usage* h_rows, uint32_t cap, bcw_usage_result* h_res) {
+  if (!x || !h_res || (cap && !h_rows)) return BCW_E_INVAL;
+  bcw_ctx* c = x->ctx;
+  DeviceGuard dg(c->device);
+  if (!dg.ok) return BCW_E_HIP;
+  void* mem = nullptr;
+  if (hipMalloc(&mem, sizeof(bcw_usage_result) + (uint64_t)cap * sizeof(bcw_fid_usage)) != hipSuccess)
+    return BCW_E_NOMEM;
+  bcw_usage_result* d_res = static_cast<bcw_usage_result*>(mem);
+  bcw_fid_usage* d_rows = cap ? reinterpret_cast<bcw_fid_usage*>(d_res + 1) : nullptr;
+  int rc = bcw_index_fid_usage_async(x, d_rows, cap, d_res);
+  if (rc == BCW_OK &&
+      (hipMemcpyAsync(h_res, d_res, sizeof *h_res, hipMemcpyDeviceToHost, c->cur) != hipSuccess ||
+       hipStreamSynchronize(c->cur) != hipSuccess))
+    rc = BCW_E_HIP;
+  if (rc == BCW_OK && (!h_res->fits || h_res->overflow)) rc = BCW_E_CAPACITY;
+  if (rc == BCW_OK && h_res->n_fids &&
+      (hipMemcpyAsync(h_rows, d_rows, h_res->n_fids * sizeof(bcw_fid_usage), hipMemcpyDeviceToHost, c->cur) !=
+           hipSuccess ||
+       hipStreamSynchronize(c->cur) != hipSuccess))
+    rc = BCW_E_HIP;
+  (void)hipStreamSynchronize(c->cur);
+  (void)hipFree(mem);
   return rc;
 }
 

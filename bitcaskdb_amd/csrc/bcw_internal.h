@@ -101,7 +101,7 @@ struct Scratch {
 // stream around every kernel of the pipeline.
 enum KernelId { K_CHASE = 0, K_CRC, K_RETIRED, K_ENC_PREP, K_ENC_SCAN, K_ENC_EVENTS, K_ENC_WRITE, K_ENC_HINT_LAYOUT,
                 K_ENC_EVENTS_HINT, K_GET_LOOKUP, K_GET_SCAN, K_GET_READ, K_PUT_PREP, K_PUT_LAYOUT, K_PUT_FRAGS,
-                K_PUT_WRITE, K_PUT_INDEX, K_NUM };
+                K_PUT_WRITE, K_PUT_INDEX, K_USAGE_INDEX, K_USAGE_ROWS, K_USAGE_FINAL, K_IX_LIVE_BYTES, K_NUM };
 struct Prof {
   uint32_t mask = 0;   // bit k: time kernel id k
   uint32_t every = 1;  // time every `every`-th launch of a selected kernel
@@ -350,6 +350,7 @@ struct bcw_ctx {
   bcw_record_table d_tab{};
   bcw_decode_result* d_result = nullptr;
   bcw_index_result* d_ires = nullptr;  // sync index calls
+  uint64_t* usage = nullptr;           // the space accounting's global table (bcw_usage.h), allocated on first use
   uint32_t last_start_off = 0;
   uint32_t chase_direct = BCW_CHASE_DIRECT_MAX;  // BCW_OPT_CHASE_DIRECT
   uint64_t test_abort_wg = 0;                    // BCW_OPT_TEST_ABORT_WAIT (one-shot)

@@ -404,11 +404,19 @@ class Index:
         return out
 
     # ---- batched Write (DBImpl.Write's writeWal + writeIndex, db_impl.go:434-480) ----
-    def write(self, active, batch, walset=None, ns_size: int = 20, etag_size: int = 20):
+    def write(self, active, batch, walset=None, ns_size: int = 20, etag_size: int = 20,
+              stats_on_device: bool = False):
         """append `batch` (write.WriteBatch) to the active WAL's resident image (write.ActiveWal) and apply it to
         this index, on the device: returns (locs, write_stats {fid: freed bytes}); see write.write_batch"""
         from .write import write_batch
-        return write_batch(self, active, batch, walset, ns_size, etag_size)
+        return write_batch(self, active, batch, walset, ns_size, etag_size, stats_on_device)
+
+    # ---- per-WAL space accounting (the compaction picker's input) ----
+    def fid_usage(self):
+        """{fid: FidUsage(count, bytes, span)} of the live keys, ascending by fid, with .soft_deleted and .invalid
+        (bcw_index_fid_usage_async: one read-only pass over the slot table); see usage.fid_usage"""
+        from .usage import fid_usage
+        return fid_usage(self)
 
     # ---- table-driven (device-resident) Put loops ----
     def recover_segment(self, data, mode: int, fid: int, start_off: int, base_time: int, ns_size: int,

@@ -142,12 +142,15 @@ class ActiveWal:
         self._mem.free()
 
 
-def write_batch(index, active: ActiveWal, batch: WriteBatch, walset=None, ns_size: int = 20, etag_size: int = 20):
+def write_batch(index, active: ActiveWal, batch: WriteBatch, walset=None, ns_size: int = 20, etag_size: int = 20,
+                stats_on_device: bool = False):
     """DBImpl.Write's writeWal + writeIndex (db_impl.go:434-480) on the device: the batch's records are encoded and
     framed into `active`'s image at its current size, the index receives Put / Delete / SoftDelete with the offsets
     the writer returned. Returns (locs [(off, size)], write_stats {FreeWalFid: FreeBytes}) as the reference's locs
     and writeStats. Raises WalError("invalid expire") / RefPanic as Record.Encode does, with nothing written and the
-    index untouched; grows the image and retries when the bytes do not fit."""
+    index untouched; grows the image and retries when the bytes do not fit.
+    stats_on_device: the WriteStat columns stay in HBM and write_stats comes from bcw_freed_by_fid_async (the same
+    dict: one row per fid instead of two columns of n entries over the bus and a host loop over them)."""
     if index.ctx is not active.ctx:
         raise ValueError("the index and the active WAL belong to different contexts")
     ws = walset if walset is not None else active.walset
@@ -190,6 +193,10 @@ def write_batch(index, active: ActiveWal, batch: WriteBatch, walset=None, ns_siz
         active.walset.put_device(active.fid, active.ptr, active.size, active.base_time)
     off = d_off.download(8 * n, dtype=np.uint64)
     size = d_size.download(8 * n, dtype=np.uint64)
+    if stats_on_device:
+        from .usage import freed_by_fid
+        return list(zip(off.tolist(), size.tolist())), freed_by_fid(index, n, d_found.ptr, d_ffid.ptr, d_fbytes.ptr,
+                                                                    d_res.ptr)
     ffid = d_ffid.download(8 * n, dtype=np.uint64)
     fbytes = d_fbytes.download(8 * n, dtype=np.uint64)
     stats: dict = {}

@@ -791,6 +791,47 @@ int64_t bcw_record_encode(uint8_t* out, uint64_t cap, const uint8_t* merged_key,
 uint64_t bcw_write_bound(uint64_t n, uint64_t keys_len, uint64_t vals_len, uint64_t metas_len, uint32_t etag_size,
                          uint64_t wal_pos);
 
+/* ---- per-WAL space accounting: live and freed bytes by fid --------------------------------------------------
+ * The numbers the compaction picker reads (maybeScheduleCompaction compaction.go:135-150 -> PickerWalInfo.FreeBytes ->
+ * DefaultCompactionPicker db.go:200-224), summed on the device: one grouped sum over rows keyed by a 64-bit fid, used
+ * for the index (what is still live in every WAL file) and for the WriteStat columns of a write (what it freed,
+ * writeIndex db_impl.go:434-454 -> manifest.Apply manifest.go:505-512). Any uint64 is a valid fid. Rows come out
+ * ascending by fid; the sums are wrapping uint64 adds, so a result does not depend on scheduling.
+ * At most BCW_USAGE_MAX_FIDS distinct fids per call (one per WAL file; the cap is part of the design, the sort of the
+ * rows runs in one workgroup's LDS): more set `overflow`, and then no row is written, the totals are 0 and n_fids is
+ * only a lower bound above the cap. */
+#define BCW_USAGE_MAX_FIDS 4096u
+typedef struct bcw_fid_usage { uint64_t fid, count, bytes, span; } bcw_fid_usage;
+typedef struct bcw_usage_result {
+  uint64_t n_fids;                /* distinct fids (exact whenever overflow == 0, also when fits == 0) */
+  uint64_t count, bytes, span;    /* totals over all rows */
+  uint64_t soft_deleted, invalid; /* index pass only */
+  uint32_t fits;                  /* 0: n_fids > cap, no row written */
+  uint32_t overflow;              /* 1: more than BCW_USAGE_MAX_FIDS distinct fids */
+} bcw_usage_result;
+/* Live usage per fid, from one pass over the index's slot table. A key is counted iff it is present and its value's
+ * off >= 40: count += 1, bytes += size (the sum of valueSize, the unit of WriteStat.FreeBytes), span +=
+ * WalRecordSize(off, size) (wal.go:61-86: the record's fragment headers and leading pad included, in constant time
+ * whatever the size), so wal.size - 40 - span is the file's exact reclaimable space. A present key with off == 0 is a
+ * SoftDelete (index.go:125-142) and counts in soft_deleted; one with 0 < off < 40, which no writer produces, in
+ * invalid; deleted and evicted keys count nowhere. Async, device-resident: d_rows (cap entries) and d_res are device
+ * pointers; runs on the index's context stream, does not synchronise and does not modify the index, whose buffers are
+ * taken at launch as for bcw_get_records_async (a call queued after a batch sees the batch). One caller at a time on
+ * the index; the scratch is the context's, so one accounting call at a time per context. */
+int bcw_index_fid_usage_async(bcw_index* ix, bcw_fid_usage* d_rows, uint32_t cap, bcw_usage_result* d_res);
+/* Synchronous, host out. Returns BCW_E_CAPACITY with the result filled when fits == 0 (retry with cap = n_fids) or
+ * overflow == 1. */
+int bcw_index_fid_usage(bcw_index* ix, bcw_fid_usage* h_rows, uint32_t cap, bcw_usage_result* h_res);
+/* The freed-bytes map of a write: writeIndex's writeStats[stat.FreeWalFid] += stat.FreeBytes (db_impl.go:434-454) over
+ * the WriteStat columns bcw_write_records_async left on the device, queued behind it on the index's context stream
+ * with no synchronisation. All n ops are grouped by free_fid, as the reference's loop does: ops that freed nothing
+ * land in the row of fid 0 with 0 bytes. count = ops with found != 0, bytes = the sum of free_bytes, span = 0.
+ * d_gate (may be NULL): the write's result on the device; when its n_written is 0 the batch was rejected, its columns
+ * were never written and are not read, and the result is empty (n_fids 0, fits 1). */
+int bcw_freed_by_fid_async(bcw_index* ix, uint64_t n, const uint8_t* d_found, const uint64_t* d_free_fid,
+                           const uint64_t* d_free_bytes, const bcw_write_result* d_gate, bcw_fid_usage* d_rows,
+                           uint32_t cap, bcw_usage_result* d_res);
+
 /* ---- host I/O staging: WAL files <-> HBM through pinned slices ---------------------------------------
  * The reference reads a segment with PreadFull per 32 KiB block (utils.go:32-48, wal_iterator.go:55)
  * and writes the rewritten WAL through a buffer flushed every >= 1 MiB (WalRewriter
