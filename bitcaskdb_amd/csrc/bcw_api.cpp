@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bcw.h"
+#include "bcw_frame.h"
 #include "bcw_internal.h"
 
 namespace bcw {
@@ -115,7 +116,7 @@ static uint32_t crc32c_hw(const uint8_t* p, size_t n) {
   while (n--) c32 = _mm_crc32_u8(c32, *p++);
   return ~c32;
 }
-static inline uint32_t mask_crc(uint32_t c) { return ((c >> 15) | (c << 17)) + 0xa282ead8u; }
+using frame::mask_crc;  // ComputeCRC32's mask (bcw_frame.h)
 
 }  // namespace bcw
 
@@ -980,12 +981,6 @@ inline void fill_rand(uint64_t& s, uint8_t* p, size_t n) {
     memcpy(p + i, &v, n - i);
   }
 }
-inline int put_uvarint(uint8_t* o, uint64_t v) {
-  int i = 0;
-  while (v >= 0x80) { o[i++] = (uint8_t)(v | 0x80); v >>= 7; }
-  o[i++] = (uint8_t)v;
-  return i;
-}
 }  // namespace
 
 int bcw_synth_segment(uint64_t target_bytes, uint64_t max_records, uint64_t seed, uint32_t ns_size,
@@ -1024,24 +1019,14 @@ int bcw_synth_segment(uint64_t target_bytes, uint64_t max_records, uint64_t seed
     } else {
       s += 0x9E3779B97F4A7C15ull * (uint64_t)(((key_len + 7) / 8) + ((vl + 7) / 8));
     }
-    // Record.Encode with no etag, no expire, no meta (record.go:57-138)
-    uint8_t tmp[30];
-    int t = 0;
-    t += put_uvarint(tmp + t, key_len);
-    t += put_uvarint(tmp + t, vl);
-    t += put_uvarint(tmp + t, 0);
-    const size_t header = (size_t)t + ns_size + 2;
-    const size_t n = header + key_len + vl;
+    // Record.Encode with no etag, no expire, no meta (record.go:57-138; only ns is read of the merged key)
+    uint8_t* r = B.rec.data();
+    size_t o = (size_t)frame::record_header_put(r, ns.data(), (uint64_t)ns_size + key_len, ns_size, vl, 0, nullptr, 0, 0,
+                                                base_time, 0);
     if (!fill) {  // the layout only (w has no output buffer: nothing is read from the record)
-      w.write_record(B.rec.data(), n, false);
+      w.write_record(r, o + key_len + vl, false);
       return;
     }
-    uint8_t* r = B.rec.data();
-    size_t o = 0;
-    r[o++] = (uint8_t)header;
-    memcpy(r + o, ns.data(), ns_size); o += ns_size;
-    r[o++] = (uint8_t)((1u << 0) | (1u << 1));  // noEtag | noExpire
-    memcpy(r + o, tmp, t); o += t;
     memcpy(r + o, B.key.data(), key_len); o += key_len;
     memcpy(r + o, B.val.data(), vl); o += vl;
     w.write_record(r, o, true);

@@ -37,10 +37,14 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "bcw_crc_dev.h"
+#include "bcw_frame.h"
 #include "bcw_internal.h"
 
 namespace bcw {
 namespace enc {
+
+using namespace frame;  // the writer's framing rules (bcw_frame.h)
 
 constexpr uint32_t kL = kBlock;           // 32768
 constexpr uint32_t kM = kBlock - kHdr;    // 32761
@@ -64,30 +68,11 @@ constexpr int kLayStride = 8;
 static_assert(kXNin == X_NIN && kXErr == X_ERR && kXNDense == X_NDENSE && kXLay == X_LAY && kXPut >= X_LAY + 2 * kLayStride,
               "emisc slots exported through bcw_internal.h");
 
-__device__ __forceinline__ uint32_t uvlen(uint64_t v) {
-  uint32_t n = 1;
-  while (v >= 0x80) { v >>= 7; ++n; }
-  return n;
-}
-__device__ __forceinline__ uint32_t uvput(uint8_t* p, uint64_t v) {
-  uint32_t n = 0;
-  while (v >= 0x80) { p[n++] = (uint8_t)(v | 0x80); v >>= 7; }
-  p[n++] = (uint8_t)v;
-  return n;
-}
-
-// a shift operator (nibble images: 8 x 16 words) applied to x
-__device__ __forceinline__ uint32_t op_apply_s(const uint32_t* __restrict__ op, uint32_t x) {
-  uint32_t r = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r ^= op[i * 16 + ((x >> (4 * i)) & 15u)];
-  return r;
-}
 // A_{8m}(x) (m zero bytes appended to a raw CRC-32C state) from the power-of-two operators p2[k] =
 // A_{8*2^k} (or their inverses: A_{8m}^-1), one operator per set bit of m
 __device__ __forceinline__ uint32_t shift_by(const uint32_t* __restrict__ p2, uint32_t x, uint64_t m) {
   for (int k = 0; m != 0 && x != 0; ++k, m >>= 1)
-    if (m & 1u) x = op_apply_s(p2 + k * 128, x);
+    if (m & 1u) x = op_apply(p2 + k * 128, x);
   return x;
 }
 
@@ -177,7 +162,7 @@ __global__ __launch_bounds__(256) void k_enc_prep(EncDev e, uint64_t rows, uint3
   uint32_t n = 0;
   if (e.mode == BCW_ENC_HINT) {
     const uint64_t off = t.foff[i] - kHdr, size = t.size[i];
-    n = e.ns + uvlen(klen) + (uint32_t)klen + uvlen(e.fid) + uvlen(off) + uvlen(size);
+    n = e.ns + uvarint_len(klen) + (uint32_t)klen + uvarint_len(e.fid) + uvarint_len(off) + uvarint_len(size);
   } else if (e.keep[i]) {
     const uint32_t flags = t.flags[i];
     const uint64_t vlen = t.val_len[i], mlen0 = t.meta_len[i], expire = t.expire[i], size = t.size[i];
@@ -191,9 +176,9 @@ __global__ __launch_bounds__(256) void k_enc_prep(EncDev e, uint64_t rows, uint3
       if (expire < e.dst_base) { atomicMin((unsigned long long*)&emisc[X_ERR], (unsigned long long)(i << 2 | BCW_ENC_ERR_EXPIRE)); sz[i] = 0; return; }
       const uint64_t d = expire - e.dst_base;
       if (d >= (1ull << 35)) { atomicMin((unsigned long long*)&emisc[X_ERR], (unsigned long long)(i << 2 | BCW_ENC_ERR_PANIC)); sz[i] = 0; return; }
-      ve = uvlen(d);
+      ve = uvarint_len(d);
     }
-    const uint64_t hn = 2 + e.ns + uvlen(klen) + uvlen(vlen) + uvlen(mlen) + el + ve;
+    const uint64_t hn = 2 + e.ns + uvarint_len(klen) + uvarint_len(vlen) + uvarint_len(mlen) + el + ve;
     n = (uint32_t)(hn + klen + vlen + mlen);
   }
   sz[i] = n;
@@ -697,22 +682,6 @@ __device__ void prog_hint(const EncDev& e, uint64_t i, uint64_t off, uint64_t si
 
 enum { PM_DST = 0, PM_HINT_DST = 1, PM_HINT_SRC = 2 };
 
-// 16 source bytes at an arbitrary address from two aligned 16 B loads (caller checks bounds)
-__device__ __forceinline__ uint4 shift16(uint4 v0, uint4 v1, uint32_t sh) {
-  // named scalars and two select stages: an array indexed by w would be lowered to a scratch round trip
-  const bool s2 = (sh & 8u) != 0, s1 = (sh & 4u) != 0;
-  const uint32_t b0 = s2 ? v0.z : v0.x, b1 = s2 ? v0.w : v0.y, b2 = s2 ? v1.x : v0.z, b3 = s2 ? v1.y : v0.w,
-                 b4 = s2 ? v1.z : v1.x, b5 = s2 ? v1.w : v1.y;
-  const uint32_t c0 = s1 ? b1 : b0, c1 = s1 ? b2 : b1, c2 = s1 ? b3 : b2, c3 = s1 ? b4 : b3, c4 = s1 ? b5 : b4;
-  const uint32_t b = sh & 3u;
-  uint4 r;
-  r.x = __builtin_amdgcn_alignbyte(c1, c0, b);
-  r.y = __builtin_amdgcn_alignbyte(c2, c1, b);
-  r.z = __builtin_amdgcn_alignbyte(c3, c2, b);
-  r.w = __builtin_amdgcn_alignbyte(c4, c3, b);
-  return r;
-}
-
 // source payload offset z -> file offset (regular records: closed form)
 __device__ __forceinline__ uint64_t src_at(uint64_t d0, uint32_t l0, uint32_t start_off, uint64_t z, uint64_t& run) {
   if (z < l0) { run = l0 - z; return d0 + z; }
@@ -774,11 +743,7 @@ __global__ __launch_bounds__(256) void k_recdesc_w(EncDev e, const uint64_t* __r
   __shared__ uint32_t s_desc[32 * 256];
   __shared__ uint32_t s_plit[12 * 256];
   const uint32_t t = threadIdx.x;
-  if (PM == PM_DST) {
-    uint32_t c = t;
-    for (int b = 0; b < 8; ++b) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
-    t0[t] = c;
-  }
+  if (PM == PM_DST) t0[t] = crc_byte_entry(t);
   __syncthreads();
   const uint64_t j = blockIdx.x * 256ull + t;
   if (j >= emisc[X_NDENSE]) return;
@@ -932,39 +897,12 @@ struct WArgs {
   uint64_t* wcnt;         // emisc + X_WL16
 };
 
-__device__ __forceinline__ uint64_t blk_end(uint64_t P) { return P + kL - (P - 40) % kL; }
-
 // the records k_wcopy writes (the others go to k_write): regular source, rcrc valid, not general, at
 // most two dst fragments
 __device__ __forceinline__ bool wcopy_item(uint32_t h1w, uint64_t P, uint64_t len) {
   if (((h1w >> 16) & 3u) != 3u || (h1w >> 24) != 0) return false;  // regular source, rcrc, not general
-  const uint64_t x1 = blk_end(P) - (P + kHdr);
+  const uint64_t x1 = frag_room(P);
   return len <= x1 || len - x1 <= kM;
-}
-
-// file offset just past a record whose first header is at P, with a payload of len > 0 bytes
-__device__ __forceinline__ uint64_t rec_end(uint64_t P, uint64_t len) {
-  const uint64_t be = blk_end(P), ds = P + kHdr;
-  if (ds + len <= be) return ds + len;
-  const uint64_t rem = len - (be - ds);
-  const uint64_t q = (rem - 1) / kM;  // whole continuation blocks before the last fragment
-  return be + q * kL + kHdr + (rem - q * kM);
-}
-
-__device__ __forceinline__ uint32_t sel_byte(uint4 v, uint32_t b) {
-  const uint32_t w = (b & 8u) ? ((b & 4u) ? v.w : v.z) : ((b & 4u) ? v.y : v.x);
-  return (w >> (8 * (b & 3u))) & 0xffu;
-}
-
-// bytes [lo, hi) of a 16 B unit
-__device__ __forceinline__ uint4 range_mask(int32_t lo, int32_t hi) {
-  uint32_t m[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int32_t a = min(max(lo - 4 * k, 0), 4), b = min(max(hi - 4 * k, 0), 4);
-    m[k] = (uint32_t)(((1ull << (8 * b)) - 1) & ~((1ull << (8 * a)) - 1));
-  }
-  return make_uint4(m[0], m[1], m[2], m[3]);
 }
 
 // 16 bytes of a wave's staged literals starting at literal offset o (-16 < o <= kWLit)
@@ -976,30 +914,12 @@ __device__ __forceinline__ uint4 lit_window(const uint32_t* __restrict__ sl, int
                     __builtin_amdgcn_alignbyte(x3, x2, sh), __builtin_amdgcn_alignbyte(x4, x3, sh));
 }
 
-// CRC-32C state after 16 more bytes (raw, slice-by-8: t8[256 k + b] = CRC of byte b and k zeros)
-__device__ __forceinline__ uint32_t crc_step16(const uint32_t* __restrict__ t8, uint32_t c, uint4 v) {
-  uint32_t x = c ^ v.x, y = v.y;
-  c = t8[1792 + (x & 0xffu)] ^ t8[1536 + ((x >> 8) & 0xffu)] ^ t8[1280 + ((x >> 16) & 0xffu)] ^ t8[1024 + (x >> 24)] ^
-      t8[768 + (y & 0xffu)] ^ t8[512 + ((y >> 8) & 0xffu)] ^ t8[256 + ((y >> 16) & 0xffu)] ^ t8[y >> 24];
-  x = c ^ v.z;
-  y = v.w;
-  return t8[1792 + (x & 0xffu)] ^ t8[1536 + ((x >> 8) & 0xffu)] ^ t8[1280 + ((x >> 16) & 0xffu)] ^ t8[1024 + (x >> 24)] ^
-         t8[768 + (y & 0xffu)] ^ t8[512 + ((y >> 8) & 0xffu)] ^ t8[256 + ((y >> 16) & 0xffu)] ^ t8[y >> 24];
-}
-
 // 16 source bytes starting at file offset S (two aligned loads; the caller checks the bounds)
 __device__ __forceinline__ uint4 src16(const uint8_t* __restrict__ seg, uint64_t S) {
   const uint64_t Ba = S & ~15ull;
   const uint4 v0 = *reinterpret_cast<const uint4*>(seg + Ba);
   const uint4 v1 = *reinterpret_cast<const uint4*>(seg + Ba + 16);
   return shift16(v0, v1, (uint32_t)(S & 15u));
-}
-
-__device__ __forceinline__ void or_masked(uint4& v, uint4 q, uint4 m) {
-  v.x |= q.x & m.x;
-  v.y |= q.y & m.y;
-  v.z |= q.z & m.z;
-  v.w |= q.w & m.w;
 }
 
 // value of the next lane in the same row of 16 (lane 15: lane 0), DPP row_ror:15
@@ -1076,11 +996,7 @@ __global__ __launch_bounds__(kWT) void k_write(WArgs A) {
   __shared__ uint32_t sp2[2][15 * 128];      // A_{8*2^k}, A_{8*2^k}^-1 (k < 15): the CRC combine
   __shared__ uint32_t s_lit[kWT / kG][kWLitWords];
   const uint32_t tid = threadIdx.x, lane = tid & 63, gl = tid & (kG - 1), gb = lane & ~(uint32_t)(kG - 1);
-  for (uint32_t i = tid; i < 256; i += kWT) {
-    uint32_t c = i;
-    for (int b = 0; b < 8; ++b) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
-    t8[i] = c;
-  }
+  crc_byte_table(t8, tid, kWT);
   for (uint32_t i = tid; i < 40 * 128; i += kWT) sop[(i >> 7) * kWopStride + (i & 127u)] = A.wops[i];
   for (uint32_t i = tid; i < 16 * 128; i += kWT) sinv[i] = A.wops[kOpInv * 128 + i];
   for (uint32_t i = tid; i < 15 * 128; i += kWT) {
@@ -1089,10 +1005,7 @@ __global__ __launch_bounds__(kWT) void k_write(WArgs A) {
   }
   for (uint32_t i = tid; i < (kWT / kG) * kWLitWords; i += kWT) (&s_lit[0][0])[i] = 0;
   __syncthreads();
-  for (uint32_t i = tid; i < 256; i += kWT) {
-    uint32_t c = t8[i];
-    for (int k = 1; k < 8; ++k) { c = (c >> 8) ^ t8[c & 0xffu]; t8[256 * k + i] = c; }
-  }
+  crc_slice_tables<8>(t8, tid, kWT);
   __syncthreads();
   uint32_t* sl = s_lit[tid / kG];
   const uint64_t ng = (uint64_t)gridDim.x * (kWT / kG);    // groups in the grid
@@ -1166,14 +1079,14 @@ __global__ __launch_bounds__(kWT) void k_write(WArgs A) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
     // zero pad before a record that starts a block (at most 6 bytes)
-    if ((P - 40) % kL == 0) {
-      const uint64_t prev = j == 0 ? pos : rec_end(Ly.fpos[j - 1], aj - Ly.da[j - 1] - kHdr);
+    if (starts_block(P)) {
+      const uint64_t prev = pad_start(j, pos, [&] { return rec_end(Ly.fpos[j - 1], aj - Ly.da[j - 1] - kHdr); });
       if (prev + gl < P) out[prev + gl - pos] = 0;
     }
 
     // CRC combine (see RecDescW): a record in one dst fragment takes rcrc; one split in two computes the
     // shorter piece's CRC and derives the other's, R(data) = A_{8y}(R(First)) ^ R(Last) (y = |Last|)
-    const uint64_t x1 = blk_end(P) - (P + kHdr);  // room in the first block
+    const uint64_t x1 = frag_room(P);  // room in the first block
     const uint32_t nfr = len <= x1 ? 1u : (len - x1 <= kM ? 2u : 3u);
     const bool comb = ((h1w >> 17) & 1u) != 0 && nfr <= 2;
     const bool direct_first = len - x1 >= x1;  // (two pieces) the First is the shorter one
@@ -1181,12 +1094,10 @@ __global__ __launch_bounds__(kWT) void k_write(WArgs A) {
     uint64_t h_first = 0;
     uint64_t hp = P, x0 = 0;
     for (bool first = true;; first = false) {  // (a zero-length First leaves x0 at 0)
-      const uint64_t be = blk_end(hp), ds = hp + kHdr;
-      const uint64_t rem = len - x0;
-      const uint64_t flen = rem < be - ds ? rem : be - ds;
-      const bool last = flen == rem;
-      const uint32_t type = first ? (last ? BCW_RECORD_FULL : BCW_RECORD_FIRST)
-                                  : (last ? BCW_RECORD_LAST : BCW_RECORD_MIDDLE);
+      const FragStep s = next_frag(hp, len - x0, first);
+      const uint64_t be = s.be, ds = s.ds, flen = s.flen;
+      const bool last = s.last;
+      const uint32_t type = s.type;
       const uint32_t ic = A.initc[flen];  // in flight during the pass
       const bool crc_on = !comb || (nfr == 2 && first == direct_first);
       uint32_t acc = 0;
@@ -1274,7 +1185,7 @@ __global__ __launch_bounds__(kWT) void k_write(WArgs A) {
             } else {
               for (int32_t b = b0; b < b1; ++b) d[b] = (uint8_t)sel_byte(v, (uint32_t)b);
             }
-            if (crc_on) c = op_apply_s(hop, c) ^ crc_step16(t8, 0u, v);
+            if (crc_on) c = op_apply(hop, c) ^ crc_step16(t8, 0u, v);
           }
           zb += kStep * kWRounds;
         }
@@ -1282,21 +1193,18 @@ __global__ __launch_bounds__(kWT) void k_write(WArgs A) {
         // shift each lane's chain to the end of the fragment's last unit (d < kG units follow it)
         if (gl < nunits) {
           const uint32_t dn = (nunits - 1 - gl) & (kG - 1);
-          if (dn & 15u) c = op_apply_s(sop + (dn & 15u) * kWopStride, c);
-          if (dn >> 4) c = op_apply_s(sop + (16u + (dn >> 4)) * kWopStride, c);
+          if (dn & 15u) c = op_apply(sop + (dn & 15u) * kWopStride, c);
+          if (dn >> 4) c = op_apply(sop + (16u + (dn >> 4)) * kWopStride, c);
         }
 #pragma unroll
         for (int m = 1; m < kG; m <<= 1) c ^= __shfl_xor(c, m, 64);
         const uint32_t t = (uint32_t)(((ul + 1) << 4) - ae);
-        acc = t ? op_apply_s(sinv + t * 128, c) : c;
+        acc = t ? op_apply(sinv + t * 128, c) : c;
         }
       }
       auto put_header = [&](uint64_t h, uint32_t r, uint32_t icv, uint64_t fl, uint32_t ty) {
         if (gl < kHdr) {
-          const uint32_t crc = ~(r ^ icv);
-          const uint32_t masked = ((crc >> 15) | (crc << 17)) + 0xa282ead8u;  // ComputeCRC32 (utils.go:24-29)
-          const uint32_t by = gl < 4 ? (masked >> (8 * gl)) : gl == 4 ? (uint32_t)fl : gl == 5 ? (uint32_t)(fl >> 8) : ty;
-          out[h - pos + gl] = (uint8_t)by;
+          out[h - pos + gl] = (uint8_t)frag_header_byte(mask_crc(~(r ^ icv)), fl, ty, gl);
         }
       };
       bool put = true;
@@ -1334,40 +1242,26 @@ __device__ void write_general_rec(const WArgs& WA, const WLay& A, uint64_t j, co
   const SrcRec sr = src_rec(e.t, e.frags, row);
   const uint64_t P = A.fpos[j];
   const uint64_t len = A.da[j + 1] - A.da[j] - kHdr;
-  if ((P - 40) % kL == 0) {
-    const uint64_t prev = j == 0 ? A.pos : rec_end(A.fpos[j - 1], A.da[j] - A.da[j - 1] - kHdr);
+  if (starts_block(P)) {
+    const uint64_t prev = pad_start(j, A.pos, [&] { return rec_end(A.fpos[j - 1], A.da[j] - A.da[j - 1] - kHdr); });
     for (uint64_t b = prev; b < P; ++b) A.out[b - A.pos] = 0;
   }
   uint64_t hp = P, z = 0;
   uint32_t q = 0;
   uint64_t qb = 0;  // payload offset of piece q
   for (bool first = true;; first = false) {
-    const uint64_t be = blk_end(hp), ds = hp + kHdr;
-    const uint64_t rem = len - z;
-    const uint64_t flen = rem < be - ds ? rem : be - ds;
-    const bool last = flen == rem;
-    const uint32_t type = first ? (last ? BCW_RECORD_FULL : BCW_RECORD_FIRST)
-                                : (last ? BCW_RECORD_LAST : BCW_RECORD_MIDDLE);
+    const FragStep s = next_frag(hp, len - z, first);
     uint32_t crc = 0xffffffffu;
-    for (uint64_t i = 0; i < flen; ++i, ++z) {
+    for (uint64_t i = 0; i < s.flen; ++i, ++z) {
       while (z >= qb + p.len[q]) { qb += p.len[q]; ++q; }
       const uint32_t by = p.src[q] ? src_byte(e.seg, e.frags, e.start_off, sr, p.off[q] + (z - qb))
                                    : plit[p.off[q] + (z - qb)];
-      A.out[ds + i - A.pos] = (uint8_t)by;
+      A.out[s.ds + i - A.pos] = (uint8_t)by;
       crc = (crc >> 8) ^ t0[(crc ^ by) & 0xffu];
     }
-    crc = ~crc;
-    const uint32_t masked = ((crc >> 15) | (crc << 17)) + 0xa282ead8u;
-    uint8_t* h = A.out + (hp - A.pos);
-    h[0] = (uint8_t)masked;
-    h[1] = (uint8_t)(masked >> 8);
-    h[2] = (uint8_t)(masked >> 16);
-    h[3] = (uint8_t)(masked >> 24);
-    h[4] = (uint8_t)flen;
-    h[5] = (uint8_t)(flen >> 8);
-    h[6] = (uint8_t)type;
-    if (last) break;
-    hp = be;
+    store_frag_header(A.out + (hp - A.pos), mask_crc(~crc), s.flen, s.type);
+    if (s.last) break;
+    hp = s.be;
   }
 }
 
@@ -1384,11 +1278,7 @@ __global__ __launch_bounds__(256) void k_write_general(WArgs WA, uint32_t li, co
   __shared__ uint32_t t0[256];
   __shared__ Prog s_prog[256];
   __shared__ uint8_t s_plit[256][48];
-  for (uint32_t i = threadIdx.x; i < 256; i += 256) {
-    uint32_t c = i;
-    for (int b = 0; b < 8; ++b) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
-    t0[i] = c;
-  }
+  crc_byte_table(t0, threadIdx.x, 256);
   __syncthreads();
   if (!lay_ok(WA.emisc, A)) return;
   for (uint64_t it = blockIdx.x * 256ull + threadIdx.x; it < nitems; it += (uint64_t)gridDim.x * 256)
@@ -1475,11 +1365,7 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
   __shared__ uint32_t sp2[2][15 * 128];  // A_{8*2^k}, A_{8*2^k}^-1
   __shared__ uint32_t s_desc[kCT / 64][32];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  {
-    uint32_t c = tid;
-    for (int b = 0; b < 8; ++b) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
-    t0[tid] = c;
-  }
+  t0[tid] = crc_byte_entry(tid);
   for (uint32_t i = tid; i < 15 * 128; i += kCT) {
     sp2[0][i] = A.wops[kOpPow2 * 128 + i];
     sp2[1][i] = A.wops[kOpPow2Inv * 128 + i];
@@ -1489,7 +1375,7 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
     uint32_t c = t0[tid];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      c = (c >> 8) ^ t0[c & 0xffu];
+      c = crc_zero_step(t0, c);
       ts[k][tid] = c;
     }
   }
@@ -1534,11 +1420,11 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
     const uint64_t d0 = uni64((uint64_t)sd[0] | ((uint64_t)sd[1] << 32));
     const uint32_t l0 = uni(sd[2]), mid_off = uni(sd[5]), npre = h1w & 0xffu, rcrc = uni(sd[31]);
     // zero pad before a record that starts a block (wal.go:509-512)
-    if ((P - 40) % kL == 0) {
-      const uint64_t prev = j == 0 ? pos : rec_end(W.fpos[j - 1], aj - W.da[j - 1] - kHdr);
+    if (starts_block(P)) {
+      const uint64_t prev = pad_start(j, pos, [&] { return rec_end(W.fpos[j - 1], aj - W.da[j - 1] - kHdr); });
       if (prev + lane < P) out[prev + lane - pos] = 0;
     }
-    const uint64_t be = blk_end(P), x1 = be - (P + kHdr);
+    const uint64_t be = blk_end(P), x1 = be - (P + kHdr);  // frag_room(P)
     const uint32_t nfr = len <= x1 ? 1u : 2u;
     uint32_t cr0 = rcrc, cr1 = 0;
     if (nfr == 2 && !(A.abl & 16)) {
@@ -1612,11 +1498,8 @@ __global__ __launch_bounds__(kCT) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
       const uint64_t fl = nfr == 1 ? len : (k == 0 ? x1 : len - x1);
       const uint32_t type = nfr == 1 ? BCW_RECORD_FULL : (k == 0 ? BCW_RECORD_FIRST : BCW_RECORD_LAST);
       if (lane < kHdr && !(A.abl & 8)) {
-        const uint32_t crc = ~((k == 0 ? cr0 : cr1) ^ A.initc[fl]);
-        const uint32_t masked = ((crc >> 15) | (crc << 17)) + 0xa282ead8u;  // ComputeCRC32 (utils.go:24-29)
-        const uint32_t by = lane < 4 ? (masked >> (8 * lane)) : lane == 4 ? (uint32_t)fl
-                          : lane == 5 ? (uint32_t)(fl >> 8) : type;
-        out[hp - pos + lane] = (uint8_t)by;
+        const uint32_t masked = mask_crc(~((k == 0 ? cr0 : cr1) ^ A.initc[fl]));
+        out[hp - pos + lane] = (uint8_t)frag_header_byte(masked, fl, type, lane);
       }
       const uint64_t dd = hp + kHdr - pos;  // out index of the fragment's data
       const uint64_t ze = x0 + fl, le = ze < npre ? ze : npre;
@@ -1658,27 +1541,17 @@ struct HintOut {
   bool first = true;
   __device__ __forceinline__ void open(uint64_t h) {  // a fragment whose header is at file offset h
     hp = h;
-    const uint64_t be = h + kL - (h - 40) % kL, ds = h + kHdr;
-    const uint64_t f = rem < be - ds ? rem : be - ds;
-    fl = (uint32_t)f;
-    type = first ? (f == rem ? BCW_RECORD_FULL : BCW_RECORD_FIRST) : (f == rem ? BCW_RECORD_LAST : BCW_RECORD_MIDDLE);
+    const FragStep s = next_frag(h, rem, first);
+    fl = (uint32_t)s.flen;
+    type = s.type;
     first = false;
-    rem -= f;
-    a = ds;
-    fend = ds + f;
+    rem -= s.flen;
+    a = s.ds;
+    fend = s.ds + s.flen;
     crc = 0xffffffffu;
   }
   __device__ __forceinline__ void close() {  // header of the current fragment
-    const uint32_t c = ~crc;
-    const uint32_t masked = ((c >> 15) | (c << 17)) + 0xa282ead8u;  // ComputeCRC32 (utils.go:24-29)
-    uint8_t* h = dst + (hp - org);
-    h[0] = (uint8_t)masked;
-    h[1] = (uint8_t)(masked >> 8);
-    h[2] = (uint8_t)(masked >> 16);
-    h[3] = (uint8_t)(masked >> 24);
-    h[4] = (uint8_t)fl;
-    h[5] = (uint8_t)(fl >> 8);
-    h[6] = (uint8_t)type;
+    store_frag_header(dst + (hp - org), mask_crc(~crc), fl, type);
   }
   __device__ __forceinline__ void put(uint32_t b) {
     while (a == fend) {  // the fragment is full (or zero-length): the next one starts at the block end
@@ -1700,11 +1573,7 @@ __global__ __launch_bounds__(256) void k_hwrite(WArgs A, uint32_t li, const uint
                                                  const uint64_t* __restrict__ dst_da, const uint64_t* __restrict__ dpos) {
   __shared__ uint32_t t0[256];
   __shared__ __attribute__((aligned(16))) uint8_t s_stage[4][kHStage];
-  {
-    uint32_t c = threadIdx.x;
-    for (int b = 0; b < 8; ++b) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
-    t0[threadIdx.x] = c;
-  }
+  t0[threadIdx.x] = crc_byte_entry(threadIdx.x);
   __syncthreads();
   const WLay& W = li ? A.w[1] : A.w[0];
   if (!lay_ok(A.emisc, W)) return;
@@ -1721,7 +1590,7 @@ __global__ __launch_bounds__(256) void k_hwrite(WArgs A, uint32_t li, const uint
     len = W.da[j + 1] - W.da[j] - kHdr;
     // the record's region starts after the previous record (the zero pad before a block start, wal.go:509-512)
     prev = P;
-    if ((P - 40) % kL == 0) prev = j == 0 ? W.pos : rec_end(W.fpos[j - 1], W.da[j] - W.da[j - 1] - kHdr);
+    if (starts_block(P)) prev = pad_start(j, W.pos, [&] { return rec_end(W.fpos[j - 1], W.da[j] - W.da[j - 1] - kHdr); });
   }
   const uint64_t end = act ? rec_end(P, len) : 0;
   // the wave's output span [lo, hi): its records are consecutive
@@ -1816,7 +1685,7 @@ __global__ __launch_bounds__(256) void k_hint_sizes(EncDev e, const uint64_t* __
   const uint64_t row = dsrc[j];
   const uint64_t klen = e.t.key_len[row];
   const uint64_t size = da[j + 1] - da[j] - kHdr;
-  hsz[j] = e.ns + uvlen(klen) + (uint32_t)klen + uvlen(e.fid) + uvlen(dpos[j]) + uvlen(size);
+  hsz[j] = e.ns + uvarint_len(klen) + (uint32_t)klen + uvarint_len(e.fid) + uvarint_len(dpos[j]) + uvarint_len(size);
 }
 
 __global__ void k_enc_finalize(const uint64_t* __restrict__ emisc, uint32_t mode, uint64_t wal_pos, uint64_t wal_cap,

@@ -39,6 +39,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "bcw_crc_dev.h"
 #include "bcw_internal.h"
 #include "bcw_read_body.h"
 #include "bcw_rules.h"
@@ -144,13 +145,8 @@ __device__ __forceinline__ uint4 load16u(const uint8_t* __restrict__ buf, uint64
 }
 // bytes [lo, hi) of a 16 B unit
 __device__ __forceinline__ uint4 keep_bytes(uint4 v, int32_t lo, int32_t hi) {
-  uint32_t m[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int32_t a = min(max(lo - 4 * k, 0), 4), b = min(max(hi - 4 * k, 0), 4);
-    m[k] = (uint32_t)(((1ull << (8 * b)) - 1) & ~((1ull << (8 * a)) - 1));
-  }
-  return make_uint4(v.x & m[0], v.y & m[1], v.z & m[2], v.w & m[3]);
+  const uint4 m = range_mask(lo, hi);
+  return make_uint4(v.x & m.x, v.y & m.y, v.z & m.z, v.w & m.w);
 }
 __device__ __forceinline__ uint4 or4(uint4 a, uint4 b) { return make_uint4(a.x | b.x, a.y | b.y, a.z | b.z, a.w | b.w); }
 
@@ -274,22 +270,6 @@ __device__ __forceinline__ uint64_t delivered_rows(const bcw_decode_result* R) {
 __device__ __forceinline__ uint32_t table_fail(const bcw_decode_result* R, uint64_t gen, uint64_t rows) {
   return R->generation != gen ? BCW_ENC_ERR_STALE
          : (R->n_records > rows || R->err_class == BCW_ERR_INTERNAL) ? BCW_ENC_ERR_TABLE : 0u;
-}
-
-// wave-aggregated add of v to *ctr; returns this lane's exclusive offset
-__device__ __forceinline__ uint64_t wave_alloc(uint64_t* ctr, uint64_t v) {
-  const uint32_t lane = threadIdx.x & 63u;
-  uint64_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t t = __shfl_up(incl, d, 64);
-    if (lane >= (uint32_t)d) incl += t;
-  }
-  const uint64_t tot = __shfl(incl, 63, 64);
-  uint64_t base = 0;
-  if (lane == 63 && tot) base = atomicAdd(reinterpret_cast<unsigned long long*>(ctr), (unsigned long long)tot);
-  base = __shfl(base, 63, 64);
-  return base + incl - v;
 }
 
 // ---- batch launch 1: key hashes ----------------------------------------------------------------

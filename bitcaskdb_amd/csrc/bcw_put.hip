@@ -21,14 +21,15 @@
 #include <cstring>
 #include <vector>
 
+#include "bcw_crc_dev.h"
+#include "bcw_frame.h"
 #include "bcw_internal.h"
-#include "bcw_read_body.h"
 
 namespace bcw {
 namespace put {
 
-constexpr uint32_t kL = kBlock;         // 32768
-constexpr uint32_t kM = kBlock - kHdr;  // 32761
+using namespace frame;  // the writer's framing rules (bcw_frame.h)
+
 // emisc slots of the write (after the layouts' slots)
 enum { P_ACC = kXPut, P_NIN = kXPut + 1, P_NFRAG = kXPut + 2, P_FOVER = kXPut + 3 };
 // k_put_prep's error classes in the two low bits of emisc[kXErr]: BCW_ENC_ERR_EXPIRE (2) and BCW_ENC_ERR_PANIC (3) as
@@ -54,32 +55,9 @@ struct PFrag {
 };
 static_assert(sizeof(PFrag) == 24, "PFrag layout");
 
-__device__ __forceinline__ uint32_t uvlen(uint64_t v) {
-  uint32_t n = 1;
-  while (v >= 0x80) { v >>= 7; ++n; }
-  return n;
-}
-__device__ __forceinline__ uint32_t uvput(uint8_t* p, uint64_t v) {
-  uint32_t n = 0;
-  while (v >= 0x80) { p[n++] = (uint8_t)(v | 0x80); v >>= 7; }
-  p[n++] = (uint8_t)v;
-  return n;
-}
-// first file offset past the block that holds P
-__device__ __forceinline__ uint64_t blk_end(uint64_t P) { return P + kL - (P - 40) % kL; }
-// file offset just past a record whose first header is at P, with a payload of len > 0 bytes
-__device__ __forceinline__ uint64_t rec_end(uint64_t P, uint64_t len) {
-  const uint64_t be = blk_end(P), ds = P + kHdr;
-  if (ds + len <= be) return ds + len;
-  const uint64_t rem = len - (be - ds);
-  const uint64_t q = (rem - 1) / kM;  // whole continuation blocks before the last fragment
-  return be + q * kL + kHdr + (rem - q * kM);
-}
-
 // ------------------------------------------------------------------------------------------
-// k_put_prep: Record.Encode's header and size per record (record.go:57-138). The literal is headerSize (truncated
-// to a byte, record.go:109) | ns | flags | uvarint(len(key)) | uvarint(len(value)) | uvarint(len(meta)) | etag |
-// uvarint(expire - baseTime), at most 2 + ns + 15 + etag + 5 bytes, kept at lit + i * lstride for the writer.
+// k_put_prep: Record.Encode's header and size per record (record.go:57-138). The literal (record_header_put,
+// bcw_frame.h; at most 2 + ns + 15 + etag + 5 bytes) is kept at lit + i * lstride for the writer.
 __global__ __launch_bounds__(256) void k_put_prep(PutDev d, uint32_t* __restrict__ sz, uint8_t* __restrict__ lit,
                                                    uint32_t* __restrict__ hlen, uint64_t* __restrict__ emisc) {
   const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
@@ -94,37 +72,12 @@ __global__ __launch_bounds__(256) void k_put_prep(PutDev d, uint32_t* __restrict
   // a record whose ranges do not lie inside the arrays is never read
   if (k0 > k1 || k1 > d.keys_len || v0 > v1 || v1 > d.vals_len || m0 > m1 || m1 > d.metas_len) return fail(kClsBatch);
   const uint64_t klm = k1 - k0, vl = v1 - v0, ml = m1 - m0;
-  const uint32_t fl = d.flags[i];
-  if (klm < d.ns || (klm | vl | ml) >> 32 || ((fl & BCW_WR_ETAG) && d.etag && !d.etags)) return fail(kClsBatch);
-  const uint64_t kl = klm - d.ns;
-  const uint32_t el = (fl & BCW_WR_ETAG) ? d.etag : 0u;
-  const uint64_t expire = d.expire[i];
-  uint32_t flag = (el == 0 ? 1u : 0u) | ((fl & BCW_WR_TOMBSTONE) ? 4u : 0u);
-  uint64_t delta = 0;
-  uint32_t ve = 0;
-  if (expire == 0) {
-    flag |= 2u;
-  } else {
-    if (expire < d.base_time) return fail(BCW_ENC_ERR_EXPIRE);
-    delta = expire - d.base_time;
-    if (delta >= (1ull << 35)) return fail(BCW_ENC_ERR_PANIC);
-    ve = uvlen(delta);
-  }
-  const uint32_t hn = 2 + d.ns + uvlen(kl) + uvlen(vl) + uvlen(ml) + el + ve;
-  const uint64_t total = (uint64_t)hn + kl + vl + ml;
-  if (total >> 32) return fail(kClsBatch);
-  uint8_t* p = lit + i * (uint64_t)d.lstride;
-  uint32_t o = 0;
-  p[o++] = (uint8_t)hn;
-  for (uint32_t b = 0; b < d.ns; ++b) p[o++] = d.keys[k0 + b];
-  p[o++] = (uint8_t)flag;
-  o += uvput(p + o, kl);
-  o += uvput(p + o, vl);
-  o += uvput(p + o, ml);
-  for (uint32_t b = 0; b < el; ++b) p[o++] = d.etags[i * (uint64_t)d.etag + b];
-  if (ve) o += uvput(p + o, delta);
-  hlen[i] = hn;
-  sz[i] = (uint32_t)total;
+  const int64_t hn = record_header_put(lit + i * (uint64_t)d.lstride, d.keys + k0, klm, d.ns, vl, ml,
+                                       d.etags ? d.etags + i * (uint64_t)d.etag : nullptr, d.etag, d.expire[i],
+                                       d.base_time, d.flags[i]);
+  if (hn < 0) return fail(hn == -BCW_ENC_ERR_BATCH ? kClsBatch : (uint32_t)-hn);
+  hlen[i] = (uint32_t)hn;
+  sz[i] = (uint32_t)((uint64_t)hn + klm - d.ns + vl + ml);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -151,22 +104,6 @@ __global__ void k_put_plan(PutDev d, uint64_t* __restrict__ emisc, bcw_write_res
   *r = o;
 }
 
-// wave-aggregated add of v to *ctr; returns this lane's exclusive offset
-__device__ __forceinline__ uint64_t wave_alloc(uint64_t* ctr, uint64_t v) {
-  const uint32_t lane = threadIdx.x & 63u;
-  uint64_t incl = v;
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    const uint64_t t = __shfl_up(incl, s, 64);
-    if (lane >= (uint32_t)s) incl += t;
-  }
-  const uint64_t tot = __shfl(incl, 63, 64);
-  uint64_t base = 0;
-  if (lane == 63 && tot) base = atomicAdd(reinterpret_cast<unsigned long long*>(ctr), (unsigned long long)tot);
-  base = __shfl(base, 63, 64);
-  return base + incl - v;
-}
-
 // ------------------------------------------------------------------------------------------
 // k_put_frags: per accepted record, locs (rec_off, rec_size: db_impl.go:475-476) and its output fragments: the
 // writer's loop (wal.go:505-549) from the record's first header, one fragment per block it touches (a block with
@@ -180,8 +117,7 @@ __global__ __launch_bounds__(256) void k_put_frags(PutDev d, const uint32_t* __r
   if (on) {
     P = dpos[j];
     len = sz[j];
-    const uint64_t x1 = blk_end(P) - (P + kHdr);  // room in the first block
-    cnt = len <= x1 ? 1 : 1 + (len - x1 + kM - 1) / kM;
+    cnt = frag_count(P, len);
   }
   uint64_t f = wave_alloc(&emisc[P_NFRAG], cnt);
   if (!on) return;
@@ -193,15 +129,11 @@ __global__ __launch_bounds__(256) void k_put_frags(PutDev d, const uint32_t* __r
   }
   uint64_t hp = P, x0 = 0;
   for (bool first = true;; first = false) {
-    const uint64_t be = blk_end(hp), ds = hp + kHdr;
-    const uint64_t rem = len - x0;
-    const uint64_t flen = rem < be - ds ? rem : be - ds;
-    const bool last = flen == rem;
-    const uint32_t type = first ? (last ? BCW_RECORD_FULL : BCW_RECORD_FIRST) : (last ? BCW_RECORD_LAST : BCW_RECORD_MIDDLE);
-    frags[f++] = PFrag{hp, (uint32_t)j, (uint32_t)x0, (uint32_t)flen, type};
-    x0 += flen;
-    if (last) break;
-    hp = be;
+    const FragStep s = next_frag(hp, len - x0, first);
+    frags[f++] = PFrag{hp, (uint32_t)j, (uint32_t)x0, (uint32_t)s.flen, s.type};
+    x0 += s.flen;
+    if (s.last) break;
+    hp = s.be;
   }
 }
 
@@ -219,13 +151,13 @@ __global__ __launch_bounds__(256) void k_put_frags(PutDev d, const uint32_t* __r
 // end are undone by A_{8t}^-1, and A_{8 flen}(~0) (initc) supplies the init value. Lanes 0-6 store the header:
 // ComputeCRC32 (utils.go:24-29), length, type.
 // LDS (32.5 KiB per workgroup of 8 waves, 2 workgroups per CU at the kernel's registers): the slice-by-8 byte tables
-// t8, the round operator A_{8*1024} as byte images, and the nibble-image operators of the final shift, laid out as
-// k_write's (bcw_encode.hip). Every table read is a ds_read_b32: 32 banks of 4 bytes, a wave
+// t8, the round operator A_{8*1024} as byte images, and the nibble-image operators of the final shift. Every table
+// read is a ds_read_b32: 32 banks of 4 bytes, a wave
 // served as two halves of 32 lanes. Operator tables are kOpStride = 144 words apart, i.e. 16 banks apart, and one
 // nibble row is 16 words, so lanes applying different operators (different dn) in the final shift collide only on
 // equal nibbles. The byte-table reads are data-dependent: 32 lanes on random banks of 32, a few ways of conflict
 // on average, which no static layout removes; replicating the 8 KiB table per lane group would, at the price of the
-// occupancy the gather's loads need, and is not done here (k_write made the same choice).
+// occupancy the gather's loads need, and is not done here.
 constexpr int kPT = 512;
 constexpr int kOpStride = 144;
 #ifndef BCW_PUT_ROUNDS
@@ -247,40 +179,6 @@ struct WArgs {
   const uint32_t* initc;  // A_{8L}(0xFFFFFFFF)
 };
 
-__device__ __forceinline__ uint32_t op_apply(const uint32_t* __restrict__ op, uint32_t x) {
-  uint32_t r = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r ^= op[i * 16 + ((x >> (4 * i)) & 15u)];
-  return r;
-}
-// the same with byte images (4 x 256 words)
-__device__ __forceinline__ uint32_t op_apply_b(const uint32_t* __restrict__ op, uint32_t x) {
-  return op[x & 0xffu] ^ op[256 + ((x >> 8) & 0xffu)] ^ op[512 + ((x >> 16) & 0xffu)] ^ op[768 + (x >> 24)];
-}
-// CRC-32C state after 16 more bytes (raw, slice-by-8: t8[256 k + b] = CRC of byte b and k zeros)
-__device__ __forceinline__ uint32_t crc_step16(const uint32_t* __restrict__ t8, uint32_t c, uint4 v) {
-  uint32_t x = c ^ v.x, y = v.y;
-  c = t8[1792 + (x & 0xffu)] ^ t8[1536 + ((x >> 8) & 0xffu)] ^ t8[1280 + ((x >> 16) & 0xffu)] ^ t8[1024 + (x >> 24)] ^
-      t8[768 + (y & 0xffu)] ^ t8[512 + ((y >> 8) & 0xffu)] ^ t8[256 + ((y >> 16) & 0xffu)] ^ t8[y >> 24];
-  x = c ^ v.z;
-  y = v.w;
-  return t8[1792 + (x & 0xffu)] ^ t8[1536 + ((x >> 8) & 0xffu)] ^ t8[1280 + ((x >> 16) & 0xffu)] ^ t8[1024 + (x >> 24)] ^
-         t8[768 + (y & 0xffu)] ^ t8[512 + ((y >> 8) & 0xffu)] ^ t8[256 + ((y >> 16) & 0xffu)] ^ t8[y >> 24];
-}
-__device__ __forceinline__ uint32_t sel_byte(uint4 v, uint32_t b) {
-  const uint32_t w = (b & 8u) ? ((b & 4u) ? v.w : v.z) : ((b & 4u) ? v.y : v.x);
-  return (w >> (8 * (b & 3u))) & 0xffu;
-}
-// bytes [lo, hi) of a 16 B unit
-__device__ __forceinline__ uint4 range_mask(int32_t lo, int32_t hi) {
-  uint32_t m[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int32_t a = min(max(lo - 4 * k, 0), 4), b = min(max(hi - 4 * k, 0), 4);
-    m[k] = (uint32_t)(((1ull << (8 * b)) - 1) & ~((1ull << (8 * a)) - 1));
-  }
-  return make_uint4(m[0], m[1], m[2], m[3]);
-}
 // the 16 bytes at address a, of which only bytes [lo, hi) are needed (0 <= lo < hi <= 16) and known to lie inside
 // the input: the aligned granule at a & ~15 is loaded when it holds one of them, and so is the next one
 __device__ __forceinline__ uint4 load_unit(uint64_t a, int32_t lo, int32_t hi) {
@@ -290,12 +188,6 @@ __device__ __forceinline__ uint4 load_unit(uint64_t a, int32_t lo, int32_t hi) {
   const uint4 v0 = (int32_t)sh + lo < 16 ? g[0] : z;
   const uint4 v1 = (int32_t)sh + hi > 16 ? g[1] : z;
   return shift16(v0, v1, sh);
-}
-__device__ __forceinline__ void or_masked(uint4& v, uint4 q, uint4 m) {
-  v.x |= q.x & m.x;
-  v.y |= q.y & m.y;
-  v.z |= q.z & m.z;
-  v.w |= q.w & m.w;
 }
 
 // a record's payload as four inputs: input s covers payload offsets [z[s], z[s + 1]) and starts at address a[s]
@@ -348,18 +240,11 @@ __global__ __launch_bounds__(kPT) void k_put_write(WArgs A) {
   __shared__ uint32_t sinv[16 * 128];  // A_{8t}^-1
   __shared__ uint32_t hopb[4 * 256];   // A_{8*1024} as byte images: the Horner step of every unit in 4 lookups, not 8
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
-  for (uint32_t i = tid; i < 256; i += kPT) {
-    uint32_t c = i;
-    for (int b = 0; b < 8; ++b) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
-    t8[i] = c;
-  }
+  crc_byte_table(t8, tid, kPT);
   for (uint32_t i = tid; i < kNOps * 128; i += kPT) sop[(i >> 7) * kOpStride + (i & 127u)] = A.wops[i];
   for (uint32_t i = tid; i < 16 * 128; i += kPT) sinv[i] = A.wops[kOpInv * 128 + i];
   __syncthreads();
-  for (uint32_t i = tid; i < 256; i += kPT) {
-    uint32_t c = t8[i];
-    for (int k = 1; k < 8; ++k) { c = (c >> 8) ^ t8[c & 0xffu]; t8[256 * k + i] = c; }
-  }
+  crc_slice_tables<8>(t8, tid, kPT);
   __syncthreads();
   {
     const uint32_t* hop = sop + 20 * kOpStride;  // A_{8*1024}, nibble images
@@ -380,8 +265,8 @@ __global__ __launch_bounds__(kPT) void k_put_write(WArgs A) {
     // defensive: the fragment lies inside the output (the layout and the plan guarantee it)
     if (hp < d.wal_pos || hp + kHdr + flen - d.wal_pos > d.wal_cap) continue;
     // zero pad before a record that starts a block (wal.go:509-512; at most 6 bytes)
-    if (F.x0 == 0 && (F.type == BCW_RECORD_FULL || F.type == BCW_RECORD_FIRST) && (hp - 40) % kL == 0) {
-      const uint64_t prev = i == 0 ? d.wal_pos : rec_end(A.dpos[i - 1], A.sz[i - 1]);
+    if (F.x0 == 0 && (F.type == BCW_RECORD_FULL || F.type == BCW_RECORD_FIRST) && starts_block(hp)) {
+      const uint64_t prev = pad_start(i, d.wal_pos, [&] { return rec_end(A.dpos[i - 1], A.sz[i - 1]); });
       if (lane < kHdr && prev + lane < hp) d.out[prev + lane - d.wal_pos] = 0;
     }
     uint32_t acc = 0;
@@ -457,10 +342,8 @@ __global__ __launch_bounds__(kPT) void k_put_write(WArgs A) {
       acc = t ? op_apply(sinv + t * 128, c) : c;
     }
     if (lane < kHdr) {
-      const uint32_t crc = ~(acc ^ A.initc[flen]);
-      const uint32_t masked = ((crc >> 15) | (crc << 17)) + 0xa282ead8u;  // ComputeCRC32 (utils.go:24-29)
-      const uint32_t by = lane < 4 ? (masked >> (8 * lane)) : lane == 4 ? (uint32_t)flen : lane == 5 ? (uint32_t)(flen >> 8) : F.type;
-      d.out[hp - d.wal_pos + lane] = (uint8_t)by;
+      const uint32_t masked = mask_crc(~(acc ^ A.initc[flen]));
+      d.out[hp - d.wal_pos + lane] = (uint8_t)frag_header_byte(masked, flen, F.type, lane);
     }
   }
 }
@@ -519,41 +402,18 @@ uint64_t bcw_write_bound(uint64_t n, uint64_t keys_len, uint64_t vals_len, uint6
 int64_t bcw_record_encode(uint8_t* out, uint64_t cap, const uint8_t* merged_key, uint64_t key_len, const uint8_t* val,
                           uint64_t val_len, const uint8_t* meta, uint64_t meta_len, const uint8_t* etag,
                           uint64_t expire, uint32_t flags, uint32_t etag_size, uint64_t base_time, uint32_t ns_size) {
-  auto uvput = [](uint8_t* p, uint64_t v) {
-    uint32_t n = 0;
-    while (v >= 0x80) { p[n++] = (uint8_t)(v | 0x80); v >>= 7; }
-    p[n++] = (uint8_t)v;
-    return n;
-  };
-  if (key_len < ns_size || (key_len | val_len | meta_len) >> 32) return -BCW_ENC_ERR_BATCH;
-  const uint32_t el = (flags & BCW_WR_ETAG) ? etag_size : 0u;
-  if (el && !etag) return -BCW_ENC_ERR_BATCH;
-  uint8_t flag = (uint8_t)((el == 0 ? 1u : 0u) | ((flags & BCW_WR_TOMBSTONE) ? 4u : 0u));
-  uint8_t exp[10], tmp[30];
-  uint32_t ve = 0;
-  if (expire == 0) flag |= 2u;
-  else if (expire < base_time) return -BCW_ENC_ERR_EXPIRE;
-  else if (expire - base_time >= (1ull << 35)) return -BCW_ENC_ERR_PANIC;
-  else ve = uvput(exp, expire - base_time);
-  const uint64_t kl = key_len - ns_size;
-  uint32_t t = uvput(tmp, kl);
-  t += uvput(tmp + t, val_len);
-  t += uvput(tmp + t, meta_len);
-  const uint64_t hn = 2ull + ns_size + t + el + ve;
-  const uint64_t total = hn + kl + val_len + meta_len;
-  if (total >> 32) return -BCW_ENC_ERR_BATCH;
+  // the header's length (or the error class) first: nothing is written into a buffer that is too small
+  const int64_t hn = frame::record_header_put(nullptr, merged_key, key_len, ns_size, val_len, meta_len, etag, etag_size,
+                                              expire, base_time, flags);
+  if (hn < 0) return hn;
+  const uint64_t kl = key_len - ns_size, total = (uint64_t)hn + kl + val_len + meta_len;
   if (total > cap || !out) return -BCW_ENC_ERR_TABLE;
-  uint64_t o = 0;
+  frame::record_header_put(out, merged_key, key_len, ns_size, val_len, meta_len, etag, etag_size, expire, base_time, flags);
+  uint64_t o = (uint64_t)hn;
   auto app = [&](const uint8_t* p, uint64_t n) {
     if (n) memcpy(out + o, p, n);
     o += n;
   };
-  out[o++] = (uint8_t)hn;  // byte(headerSize): truncates above 255 (record.go:109)
-  app(merged_key, ns_size);
-  out[o++] = flag;
-  app(tmp, t);
-  app(etag, el);
-  app(exp, ve);
   app(merged_key + ns_size, kl);
   app(val, val_len);
   app(meta, meta_len);

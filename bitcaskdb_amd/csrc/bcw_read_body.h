@@ -8,21 +8,12 @@
 
 #include <cstdint>
 
+#include "bcw_crc_dev.h"
+#include "bcw_frame.h"
 #include "bcw_internal.h"
 #include "bcw_parse.h"
 
 namespace bcw {
-
-// bytes [sh, sh + 16) of the 32 bytes v0 || v1
-__device__ __forceinline__ uint4 shift16(uint4 v0, uint4 v1, uint32_t sh) {
-  const bool s2 = (sh & 8u) != 0, s1 = (sh & 4u) != 0;
-  const uint32_t b0 = s2 ? v0.z : v0.x, b1 = s2 ? v0.w : v0.y, b2 = s2 ? v1.x : v0.z, b3 = s2 ? v1.y : v0.w,
-                 b4 = s2 ? v1.z : v1.x, b5 = s2 ? v1.w : v1.y;
-  const uint32_t c0 = s1 ? b1 : b0, c1 = s1 ? b2 : b1, c2 = s1 ? b3 : b2, c3 = s1 ? b4 : b3, c4 = s1 ? b5 : b4;
-  const uint32_t b = sh & 3u;
-  return make_uint4(__builtin_amdgcn_alignbyte(c1, c0, b), __builtin_amdgcn_alignbyte(c2, c1, b),
-                    __builtin_amdgcn_alignbyte(c3, c2, b), __builtin_amdgcn_alignbyte(c4, c3, b));
-}
 
 namespace rd {
 
@@ -67,13 +58,6 @@ struct FragReader {
     return 0;
   }
 };
-
-__device__ __forceinline__ uint32_t apply_nib(const uint32_t* __restrict__ t, uint32_t x) {
-  uint32_t r = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r ^= t[i * 16 + ((x >> (4 * i)) & 15u)];
-  return r;
-}
 
 // what a request reads from: the WAL image, the verify tables in LDS (t0: the CRC-32C byte table, sp2: kPow2Ops
 // nibble images of A_{8 * 2^k}) and in HBM (initc), and the wave's fragment list in LDS (kMaxF entries each)
@@ -172,7 +156,7 @@ __device__ __forceinline__ uint32_t read_walk(const ReadEnv& E, uint64_t off, ui
       if (a0 < a1) {
         uint64_t dsh = len - a1;  // zero bytes after the chunk
         for (int k = 0; dsh; ++k, dsh >>= 1)
-          if (dsh & 1u) x = apply_nib(E.sp2 + k * 128, x);
+          if (dsh & 1u) x = op_apply(E.sp2 + k * 128, x);
       } else {
         x = 0;
       }
@@ -181,10 +165,9 @@ __device__ __forceinline__ uint32_t read_walk(const ReadEnv& E, uint64_t off, ui
       // the init contribution A_{8L}(~0): the table up to one block, beyond (crafted lengths) by shifts
       uint32_t ic = E.initc[len <= kBlock ? len : kBlock];
       for (uint64_t dsh = len > kBlock ? len - kBlock : 0, k = 0; dsh; ++k, dsh >>= 1)
-        if (dsh & 1u) ic = apply_nib(E.sp2 + k * 128, ic);
-      const uint32_t c32 = ~(x ^ ic);  // CRC-32C = ~crc_update(~0, data)
-      const uint32_t masked = ((c32 >> 15) | (c32 << 17)) + 0xa282ead8u;  // ComputeCRC32 (utils.go:24-29)
-      if (masked != crc) { st = BCW_RD_CRC; break; }
+        if (dsh & 1u) ic = op_apply(E.sp2 + k * 128, ic);
+      // CRC-32C = ~crc_update(~0, data)
+      if (frame::mask_crc(~(x ^ ic)) != crc) { st = BCW_RD_CRC; break; }
     }
     got += len;
     if (type == BCW_RECORD_FULL || type == BCW_RECORD_LAST) {
@@ -200,11 +183,7 @@ __device__ __forceinline__ uint32_t read_walk(const ReadEnv& E, uint64_t off, ui
 // fill the LDS verify tables of a workgroup of `threads` threads (the caller's __syncthreads follows)
 __device__ __forceinline__ void load_verify_tables(uint32_t* t0, uint32_t* sp2, const uint32_t* __restrict__ pow2,
                                                    uint32_t tid, uint32_t threads) {
-  for (uint32_t i = tid; i < 256; i += threads) {
-    uint32_t c = i;
-    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
-    t0[i] = c;
-  }
+  crc_byte_table(t0, tid, threads);
   for (uint32_t i = tid; i < kPow2Ops * 128; i += threads) sp2[i] = pow2[i];
 }
 
