@@ -16,7 +16,7 @@ from .staging import Stage
 from .index import (ErrKeyNotFound, ErrKeySoftDeleted, GetBatch, Index, WalSet, compact_one_wal_filtered, merged_key,
                     murmur3_sum64, recover_from_wals)
 from .write import ActiveWal, WriteBatch
-from .usage import FidUsage, PickerWalInfo, default_compaction_picker, wal_garbage
+from .usage import FidUsage, FidUsageMap, PickerWalInfo, default_compaction_picker, drop_fids, wal_garbage
 
 __all__ = ["Context", "Decoded", "ErrCorruptedHintRecord", "ErrInvalidData", "ErrShortFile",
            "ErrWalMismatchBlockSize", "ErrWalMismatchCRC", "ErrWalMismatchMagic", "ErrWalUnknownRecordType",
@@ -24,4 +24,5 @@ __all__ = ["Context", "Decoded", "ErrCorruptedHintRecord", "ErrInvalidData", "Er
            "iterate_hint", "iterate_record", "load_wal", "_lib", "WalFile", "compact_one_wal",
            "new_hint_by_wal", "ErrKeyNotFound", "ErrKeySoftDeleted", "Index", "compact_one_wal_filtered",
            "merged_key", "murmur3_sum64", "recover_from_wals", "Stage", "WalSet", "GetBatch", "ActiveWal",
-           "WriteBatch", "FidUsage", "PickerWalInfo", "default_compaction_picker", "wal_garbage"]
+           "WriteBatch", "FidUsage", "PickerWalInfo", "default_compaction_picker", "wal_garbage",
+           "FidUsageMap", "drop_fids"]

@@ -187,7 +187,8 @@ IDX_FOUND, IDX_NOT_FOUND, IDX_SOFT_DELETED = 0, 1, 2
 IDX_ERR_FULL = 6
 RULE_EXPIRED, RULE_TOMBSTONE, RULE_PREFIX = 1, 2, 4  # bcw_compact_rules.mask
 RULE_MAX_PREFIXES, RULE_MAX_PREFIX_LEN = 64, 64
-USAGE_MAX_FIDS = 4096  # bcw_index_fid_usage* / bcw_freed_by_fid_async: distinct fids per call
+USAGE_MAX_FIDS = 4096  # bcw_index_fid_usage* / bcw_freed_by_fid_async / bcw_index_drop_fids*: distinct fids per call
+DROP_IN, DROP_NOT_IN = 0, 1  # bcw_index_drop_fids* mode
 RECOVER_NOT_RUN, RECOVER_HINT, RECOVER_HINT_WAL, RECOVER_WAL = 0, 1, 2, 3
 RD_OK, RD_BEYOND, RD_CORRUPTED, RD_CRC, RD_SIZE, RD_TYPE, RD_INCOMPLETE, RD_PANIC = range(8)
 GET_OK, GET_NOT_FOUND, GET_SOFT_DELETED, GET_NO_WAL, GET_READ, GET_RECORD = range(6)
@@ -278,6 +279,9 @@ def _load():
         "bcw_index_fid_usage_async": (C.c_int, [vp, vp, C.c_uint32, vp]),
         "bcw_index_fid_usage": (C.c_int, [vp, C.POINTER(FidUsageRow), C.c_uint32, C.POINTER(UsageResult)]),
         "bcw_freed_by_fid_async": (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp, vp, C.c_uint32, vp]),
+        "bcw_index_drop_fids_async": (C.c_int, [vp, C.c_int, u64p, C.c_uint32, vp, C.c_uint32, vp]),
+        "bcw_index_drop_fids": (C.c_int, [vp, C.c_int, u64p, C.c_uint32, C.POINTER(FidUsageRow), C.c_uint32,
+                                          C.POINTER(UsageResult)]),
         "bcw_record_encode": (C.c_int64, [vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp,
                                           C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
         "bcw_write_bound": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64]),

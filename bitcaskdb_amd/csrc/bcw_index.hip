@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "bcw_crc_dev.h"
+#include "bcw_drop.h"
 #include "bcw_internal.h"
 #include "bcw_read_body.h"
 #include "bcw_rules.h"
@@ -856,24 +857,15 @@ __global__ void k_ix_adopt(uint64_t* __restrict__ cnt) {
 
 // ---- export of the live entries (the Go shim loads them into its ShardMap after a GPU rebuild) --------
 // fids (sorted, nf > 0): only entries whose value fid is one of them (the slice of the index that points into
-// a set of WAL files: the compaction fan-out's filter snapshot)
-__device__ __forceinline__ bool fid_in(const uint64_t* __restrict__ fids, uint32_t nf, uint64_t f) {
-  if (nf == 0) return true;
-  uint32_t lo = 0, hi = nf;
-  while (lo < hi) {
-    const uint32_t m = (lo + hi) >> 1;
-    if (fids[m] < f) lo = m + 1; else hi = m;
-  }
-  return lo < nf && fids[lo] == f;
-}
-
+// a set of WAL files: the compaction fan-out's filter snapshot); nf == 0: every entry. The membership test is
+// bcw_drop.h's.
 __global__ __launch_bounds__(256) void k_ix_count(const Slot* __restrict__ slots, uint64_t cap,
                                                   const uint8_t* __restrict__ arena, const uint64_t* __restrict__ fids,
                                                   uint32_t nf, uint64_t* __restrict__ blk_n,
                                                   uint64_t* __restrict__ blk_b) {
   const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
   uint64_t c = 0, b = 0;
-  if (i < cap && slots[i].kref && slots[i].live && fid_in(fids, nf, slots[i].fid)) {
+  if (i < cap && slots[i].kref && slots[i].live && (nf == 0 || drop::fid_in(fids, nf, slots[i].fid))) {
     c = 1;
     b = *reinterpret_cast<const uint32_t*>(arena + (slots[i].kref - 1) + 8);
   }
@@ -900,7 +892,7 @@ __global__ __launch_bounds__(256) void k_ix_export(const Slot* __restrict__ slot
   uint64_t c = 0, b = 0;
   Slot S{};
   if (i < cap) S = slots[i];
-  const bool act = i < cap && S.kref && S.live && fid_in(fids, nf, S.fid);
+  const bool act = i < cap && S.kref && S.live && (nf == 0 || drop::fid_in(fids, nf, S.fid));
   if (act) {
     c = 1;
     b = *reinterpret_cast<const uint32_t*>(arena + (S.kref - 1) + 8);
@@ -999,11 +991,43 @@ __global__ __launch_bounds__(1024) void k_ix_evict(Slot* __restrict__ slots, uin
 // ---- live usage per fid (bcw_index_fid_usage*, bcw_usage.h): one read-only pass over the slot table ----------
 // A workgroup takes 256 slots per round: their 16 KiB go through LDS as 1024 contiguous 16 B loads (every lane's load
 // next to its neighbour's; a slot's four chunks land rotated by its index so that the lanes' 16 B reads of one field
-// pair spread over all banks), then each lane reads {fid}, {off, size}, {live} of its own slot. A slot is counted iff
-// live and off >= 40; its span is WalRecordSize in closed form (the size is not trusted). Rows go to the workgroup's
+// pair spread over all banks), then each lane reads {fid}, {off, size}, {live} of its own slot (usage_round: the one
+// text of that round, compiled by this pass and by its writing twin, k_ix_drop). A slot is counted iff live and
+// off >= 40; its span is WalRecordSize in closed form (the size is not trusted). Rows go to the workgroup's
 // accumulator; soft-deleted (live, off == 0) and invalid (live, 0 < off < 40) slots are only counted.
 constexpr uint32_t kUsageSlots = usage::kThreads;  // slots per workgroup round
 __device__ __forceinline__ uint32_t usage_chunk_pos(uint32_t slot, uint32_t q) { return slot * 4 + (q ^ ((slot >> 2) & 3u)); }
+
+struct UsageLane {  // what a lane holds of its slot after a round; live is false for a lane past the table's end
+  bool live;
+  uint64_t fid, off, size;
+};
+
+// one round: slots [base, base + 256) of the table (fewer at its end) through `stage` (kUsageSlots * 4 chunks), every
+// thread of the workgroup calls it; the lane's slot is base + threadIdx.x
+__device__ __forceinline__ UsageLane usage_round(const Slot* __restrict__ slots, uint64_t cap, uint64_t base,
+                                                 uint4* __restrict__ stage) {
+  const uint32_t tid = threadIdx.x;
+  const uint64_t left = cap - base;
+  const uint32_t nslots = left < kUsageSlots ? (uint32_t)left : kUsageSlots;
+  const uint4* __restrict__ src = reinterpret_cast<const uint4*>(slots + base);
+#pragma unroll
+  for (uint32_t k = 0; k < 4; ++k) {
+    const uint32_t j = k * usage::kThreads + tid;  // chunk j of the round: slot j / 4, 16 B part j % 4
+    if (j < nslots * 4) stage[usage_chunk_pos(j >> 2, j & 3u)] = src[j];
+  }
+  __syncthreads();
+  const bool valid = tid < nslots;
+  const uint4 hf = stage[usage_chunk_pos(tid, 1)], os = stage[usage_chunk_pos(tid, 2)],
+              lp = stage[usage_chunk_pos(tid, 3)];
+  __syncthreads();  // the next round overwrites the staging buffer
+  UsageLane r;
+  r.fid = (uint64_t)hf.z | ((uint64_t)hf.w << 32);
+  r.off = (uint64_t)os.x | ((uint64_t)os.y << 32);
+  r.size = (uint64_t)os.z | ((uint64_t)os.w << 32);
+  r.live = valid && (lp.x | lp.y) != 0;
+  return r;
+}
 
 __global__ __launch_bounds__(usage::kThreads) void k_ix_usage(const Slot* __restrict__ slots, uint64_t cap,
                                                               uint64_t* __restrict__ scratch) {
@@ -1014,27 +1038,12 @@ __global__ __launch_bounds__(usage::kThreads) void k_ix_usage(const Slot* __rest
   const uint32_t tid = threadIdx.x;
   uint64_t n_soft = 0, n_inv = 0;
   for (uint64_t base = (uint64_t)blockIdx.x * kUsageSlots; base < cap; base += (uint64_t)gridDim.x * kUsageSlots) {
-    const uint64_t left = cap - base;
-    const uint32_t nslots = left < kUsageSlots ? (uint32_t)left : kUsageSlots;
-    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(slots + base);
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) {
-      const uint32_t j = k * usage::kThreads + tid;  // chunk j of the round: slot j / 4, 16 B part j % 4
-      if (j < nslots * 4) stage[usage_chunk_pos(j >> 2, j & 3u)] = src[j];
-    }
-    __syncthreads();
-    const bool valid = tid < nslots;
-    const uint4 hf = stage[usage_chunk_pos(tid, 1)], os = stage[usage_chunk_pos(tid, 2)],
-                lp = stage[usage_chunk_pos(tid, 3)];
-    __syncthreads();  // the next round overwrites the staging buffer
-    const uint64_t fid = (uint64_t)hf.z | ((uint64_t)hf.w << 32);
-    const uint64_t off = (uint64_t)os.x | ((uint64_t)os.y << 32), size = (uint64_t)os.z | ((uint64_t)os.w << 32);
-    const bool live = valid && (lp.x | lp.y) != 0;
-    const bool counted = live && off >= BCW_SUPER_BLOCK_SIZE;
-    n_soft += (live && off == 0) ? 1 : 0;
-    n_inv += (live && off != 0 && off < BCW_SUPER_BLOCK_SIZE) ? 1 : 0;
-    const uint64_t span = counted ? usage::wal_record_size_closed(off, size) : 0;
-    acc.add(g, counted, fid, true, size, span);
+    const UsageLane r = usage_round(slots, cap, base, stage);
+    const bool counted = r.live && r.off >= BCW_SUPER_BLOCK_SIZE;
+    n_soft += (r.live && r.off == 0) ? 1 : 0;
+    n_inv += (r.live && r.off != 0 && r.off < BCW_SUPER_BLOCK_SIZE) ? 1 : 0;
+    const uint64_t span = counted ? usage::wal_record_size_closed(r.off, r.size) : 0;
+    acc.add(g, counted, r.fid, true, r.size, span);
   }
   acc.flush(g);
 #pragma unroll
@@ -1046,6 +1055,59 @@ __global__ __launch_bounds__(usage::kThreads) void k_ix_usage(const Slot* __rest
     if (n_soft) atomicAdd(&g.aux[usage::A_SOFT], (unsigned long long)n_soft);
     if (n_inv) atomicAdd(&g.aux[usage::A_INVALID], (unsigned long long)n_inv);
   }
+}
+
+// ---- retiring WAL files (bcw_index_drop_fids*, bcw_drop.h): the writing twin of k_ix_usage -------------------------
+// The same rounds. The fid list (ascending, distinct, at most BCW_USAGE_MAX_FIDS) is searched from dynamic LDS sized
+// to the list, so a list of the one to three files of a compaction leaves the workgroup's LDS, and with it the
+// occupancy, at k_ix_usage's; the [min, max] range test comes before the search. A wave in which no lane is selected
+// (the ballot) does no accumulator work and stores nothing. A selected lane stores the 8 bytes of its slot's `live`
+// (every slot belongs to one lane of one workgroup: no other thread of the pass reads or writes it) and feeds the
+// accumulator by k_ix_usage's counting rule; each wave adds its dropped count to a word of LDS and the workgroup takes
+// the sum off C_LIVE with one atomic at the end (one atomic per wave was measured: 8,192 adds to one address took
+// longer than the pass itself).
+// The stores and the C_LIVE count do not depend on the accounting table (an overflow voids only rows and totals).
+__global__ __launch_bounds__(usage::kThreads) void k_ix_drop(Slot* __restrict__ slots, uint64_t cap,
+                                                             const uint64_t* __restrict__ d_fids, uint32_t nf,
+                                                             int mode, uint64_t* __restrict__ scratch,
+                                                             uint64_t* __restrict__ cnt) {
+  __shared__ usage::Accum acc;
+  __shared__ uint4 stage[kUsageSlots * 4];
+  extern __shared__ uint64_t s_fids[];  // nf entries
+  __shared__ unsigned long long s_drop;
+  const uint32_t tid = threadIdx.x;
+  if (tid == 0) s_drop = 0;
+  for (uint32_t i = tid; i < nf; i += usage::kThreads) s_fids[i] = d_fids[i];
+  acc.init();  // ends with the barrier that publishes the list too
+  const usage::Table g = usage::table_of(scratch);
+  uint64_t n_soft = 0, n_inv = 0, n_drop = 0;
+  for (uint64_t base = (uint64_t)blockIdx.x * kUsageSlots; base < cap; base += (uint64_t)gridDim.x * kUsageSlots) {
+    const UsageLane r = usage_round(slots, cap, base, stage);
+    n_soft += (r.live && r.off == 0) ? 1 : 0;
+    const bool file = r.live && r.off != 0;  // only these are searched
+    const bool sel = drop::selected(mode, r.live, r.off, file && drop::fid_in_range(s_fids, nf, r.fid));
+    if (__ballot(sel) == 0) continue;  // wave-uniform
+    const bool counted = sel && r.off >= BCW_SUPER_BLOCK_SIZE;
+    n_drop += sel ? 1 : 0;
+    n_inv += (sel && !counted) ? 1 : 0;
+    if (sel) slots[base + tid].live = 0;  // sel implies a lane inside the table
+    const uint64_t span = counted ? usage::wal_record_size_closed(r.off, r.size) : 0;
+    acc.add(g, counted, r.fid, true, r.size, span);
+  }
+  acc.flush(g);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    n_soft += __shfl_xor(n_soft, d, 64);
+    n_inv += __shfl_xor(n_inv, d, 64);
+    n_drop += __shfl_xor(n_drop, d, 64);
+  }
+  if ((tid & 63u) == 0) {
+    if (n_soft) atomicAdd(&g.aux[usage::A_SOFT], (unsigned long long)n_soft);
+    if (n_inv) atomicAdd(&g.aux[usage::A_INVALID], (unsigned long long)n_inv);
+    if (n_drop) atomicAdd(&s_drop, (unsigned long long)n_drop);
+  }
+  __syncthreads();
+  if (tid == 0 && s_drop) atomicAdd(reinterpret_cast<unsigned long long*>(&cnt[C_LIVE]), 0ull - s_drop);
 }
 
 }  // namespace ix
@@ -1084,6 +1146,12 @@ struct bcw_index {
   rules::PrefixTable* d_rule_tab = nullptr;
   uint64_t* d_rule_cnt = nullptr;
   uint64_t rule_host[3] = {0, 0, 0};
+  // the fid list of bcw_index_drop_fids* (allocated with the first drop, BCW_USAGE_MAX_FIDS entries each): the
+  // normalised list in pinned host memory, its device copy, and the event behind the last copy out of the pinned
+  // buffer, which the next call waits for before it overwrites the buffer (the copy alone, not the stream)
+  uint64_t* drop_h = nullptr;
+  uint64_t* drop_d = nullptr;
+  hipEvent_t drop_ev = nullptr;
 };
 
 namespace bcw {
@@ -1508,8 +1576,10 @@ int bcw_index_destroy(bcw_index* x) {
   DeviceGuard dg(x->ctx->device);
   (void)hipStreamSynchronize(x->ctx->cur);
   void* ptrs[] = {x->slots, x->arena, x->cnt, x->op_kref, x->op_hash, x->op_slot, x->stage, x->d_res,
-                  x->d_rule_tab, x->d_rule_cnt};
+                  x->d_rule_tab, x->d_rule_cnt, x->drop_d};
   for (void* q : ptrs) (void)hipFree(q);
+  if (x->drop_h) (void)hipHostFree(x->drop_h);
+  if (x->drop_ev) (void)hipEventDestroy(x->drop_ev);
   delete x;
   return BCW_OK;
 }
@@ -1891,6 +1961,87 @@ int bcw_index_fid_usage(bcw_index* x, bcw_fid_usage* h_rows, uint32_t cap, bcw_u
     rc = BCW_E_HIP;
   if (rc == BCW_OK && (!h_res->fits || h_res->overflow)) rc = BCW_E_CAPACITY;
   if (rc == BCW_OK && h_res->n_fids &&
+      (hipMemcpyAsync(h_rows, d_rows, h_res->n_fids * sizeof(bcw_fid_usage), hipMemcpyDeviceToHost, c->cur) !=
+           hipSuccess ||
+       hipStreamSynchronize(c->cur) != hipSuccess))
+    rc = BCW_E_HIP;
+  (void)hipStreamSynchronize(c->cur);
+  (void)hipFree(mem);
+  return rc;
+}
+
+int bcw_index_drop_fids_async(bcw_index* x, int mode, const uint64_t* h_fids, uint32_t n_fids, bcw_fid_usage* d_rows,
+                              uint32_t cap, bcw_usage_result* d_res) {
+  if (!x || !d_res || (cap && !d_rows)) return BCW_E_INVAL;
+  std::vector<uint64_t> fids;
+  int rc = drop::normalise(mode, h_fids, n_fids, &fids);  // nothing has touched the index or the stream yet
+  if (rc != BCW_OK) return rc;
+  const uint32_t nf = (uint32_t)fids.size();
+  bcw_ctx* c = x->ctx;
+  DeviceGuard dg(c->device);
+  if (!dg.ok) return BCW_E_HIP;
+  hipStream_t st = c->cur;
+  if (!x->drop_d) {
+    const size_t bytes = (size_t)BCW_USAGE_MAX_FIDS * sizeof(uint64_t);
+    // the list alone can pass 64 KiB of LDS per workgroup together with the kernel's static 32 KiB
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ix_drop), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)bytes);
+    (void)hipGetLastError();
+    if (hipMalloc(&x->drop_d, bytes) != hipSuccess) {
+      x->drop_d = nullptr;
+      return BCW_E_NOMEM;
+    }
+    if (hipHostMalloc(&x->drop_h, bytes, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&x->drop_ev, hipEventDisableTiming) != hipSuccess) {
+      if (x->drop_h) (void)hipHostFree(x->drop_h);
+      (void)hipFree(x->drop_d);
+      x->drop_h = x->drop_d = nullptr;
+      x->drop_ev = nullptr;
+      return BCW_E_NOMEM;
+    }
+  } else if (hipEventSynchronize(x->drop_ev) != hipSuccess) {  // the previous call's copy has read the pinned list
+    return BCW_E_HIP;
+  }
+  if (nf) {
+    memcpy(x->drop_h, fids.data(), (size_t)nf * sizeof(uint64_t));
+    if (hipMemcpyAsync(x->drop_d, x->drop_h, (size_t)nf * sizeof(uint64_t), hipMemcpyHostToDevice, st) != hipSuccess)
+      return BCW_E_HIP;
+  }
+  if (hipEventRecord(x->drop_ev, st) != hipSuccess) return BCW_E_HIP;
+  uint64_t* scratch = nullptr;
+  rc = usage_begin(c, st, &scratch);
+  if (rc != BCW_OK) return rc;
+  if (x->slots && x->cap) {  // the buffers as they are now, as bcw_index_fid_usage_async takes them
+    const uint64_t wgs = (x->cap + kUsageSlots - 1) / kUsageSlots;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(wgs, (uint64_t)c->num_cus * 8);
+    hipEvent_t ev = nullptr;
+    c->prof.begin(K_IX_DROP, st, ev);
+    k_ix_drop<<<grid, usage::kThreads, (size_t)nf * sizeof(uint64_t), st>>>(x->slots, x->cap, x->drop_d, nf, mode,
+                                                                           scratch, x->cnt);
+    c->prof.end(K_IX_DROP, st, ev);
+    if (hipGetLastError() != hipSuccess) return BCW_E_HIP;
+  }
+  return usage_finish(c, st, d_rows, cap, d_res, 1);
+}
+
+int bcw_index_drop_fids(bcw_index* x, int mode, const uint64_t* h_fids, uint32_t n_fids, bcw_fid_usage* h_rows,
+                        uint32_t cap, bcw_usage_result* h_res) {
+  if (!x || !h_res || (cap && !h_rows)) return BCW_E_INVAL;
+  bcw_ctx* c = x->ctx;
+  DeviceGuard dg(c->device);
+  if (!dg.ok) return BCW_E_HIP;
+  void* mem = nullptr;
+  if (hipMalloc(&mem, sizeof(bcw_usage_result) + (uint64_t)cap * sizeof(bcw_fid_usage)) != hipSuccess)
+    return BCW_E_NOMEM;
+  bcw_usage_result* d_res = static_cast<bcw_usage_result*>(mem);
+  bcw_fid_usage* d_rows = cap ? reinterpret_cast<bcw_fid_usage*>(d_res + 1) : nullptr;
+  int rc = bcw_index_drop_fids_async(x, mode, h_fids, n_fids, d_rows, cap, d_res);
+  if (rc == BCW_OK &&
+      (hipMemcpyAsync(h_res, d_res, sizeof *h_res, hipMemcpyDeviceToHost, c->cur) != hipSuccess ||
+       hipStreamSynchronize(c->cur) != hipSuccess))
+    rc = BCW_E_HIP;
+  // fits == 0 and overflow are the caller's to read: the drop has happened either way
+  if (rc == BCW_OK && h_res->fits && !h_res->overflow && h_res->n_fids &&
       (hipMemcpyAsync(h_rows, d_rows, h_res->n_fids * sizeof(bcw_fid_usage), hipMemcpyDeviceToHost, c->cur) !=
            hipSuccess ||
        hipStreamSynchronize(c->cur) != hipSuccess))

@@ -418,6 +418,21 @@ class Index:
         from .usage import fid_usage
         return fid_usage(self)
 
+    # ---- retiring WAL files (compaction's deleteFiles, reclaimDiskUsage) ----
+    def drop_fids(self, fids):
+        """remove every entry whose value lives in one of the WAL files `fids` (files that were deleted): the entries
+        become what a Delete leaves, soft-deleted keys stay. Returns the FidUsageMap of what was dropped, with
+        .invalid and .soft_deleted (bcw_index_drop_fids, BCW_DROP_IN); see usage.drop_fids"""
+        from .usage import drop_fids
+        return drop_fids(self, fids, L.DROP_IN)
+
+    def retain_fids(self, fids):
+        """keep only the entries whose value lives in one of the WAL files `fids` (the files that exist) and the
+        soft-deleted keys; returns the FidUsageMap of what was dropped (bcw_index_drop_fids, BCW_DROP_NOT_IN): the
+        one-pass resync after load_snapshot of an index that still names deleted files"""
+        from .usage import drop_fids
+        return drop_fids(self, fids, L.DROP_NOT_IN)
+
     # ---- table-driven (device-resident) Put loops ----
     def recover_segment(self, data, mode: int, fid: int, start_off: int, base_time: int, ns_size: int,
                         etag_size: int, use_record_fid: bool = False):

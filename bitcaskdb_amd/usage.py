@@ -25,6 +25,7 @@ class FidUsageMap(dict):
     and invalid (present keys with 0 < off < 40, which no writer produces)"""
     soft_deleted = 0
     invalid = 0
+    overflow = False  # drop_fids only: more distinct fids than the accounting holds, the rows are void
 
 
 class PickerWalInfo(NamedTuple):  # compaction.go:135-150
@@ -64,6 +65,34 @@ def fid_usage(index) -> FidUsageMap:
         finally:
             d_rows.free()
             d_res.free()
+
+
+def drop_fids(index, fids, mode: int = L.DROP_IN) -> FidUsageMap:
+    """bcw_index_drop_fids: remove every file-backed entry whose fid is in `fids` (DROP_IN: the files that were
+    deleted) or is not in it (DROP_NOT_IN: keep only the files that exist), in one pass over the slot table on the
+    index's stream. Returns what was dropped as fid_usage reports it, {fid: FidUsage} ascending, with .invalid (dropped
+    entries with 0 < off < 40) and .soft_deleted (soft-deleted entries, which always stay). The call cannot be
+    repeated, so the row buffer holds the most rows it can return; where a DROP_NOT_IN call met more than
+    BCW_USAGE_MAX_FIDS distinct dead fids the drop is still complete and the map comes back empty with .overflow set.
+    ValueError for a list of more than BCW_USAGE_MAX_FIDS distinct fids or an unknown mode (the index is untouched)."""
+    import numpy as np
+    fa = np.ascontiguousarray([int(f) for f in fids], dtype=np.uint64)
+    nf = int(fa.size)
+    cap = max(min(nf, L.USAGE_MAX_FIDS), 1) if mode == L.DROP_IN else L.USAGE_MAX_FIDS
+    rows, res = (L.FidUsageRow * cap)(), L.UsageResult()
+    rc = L.lib.bcw_index_drop_fids(index.handle, mode, fa.ctypes.data_as(L.u64p) if nf else None, nf, rows, cap,
+                                   C.byref(res))
+    if rc == L.E_INVAL:
+        raise ValueError(f"bcw_index_drop_fids: mode {mode} or more than {L.USAGE_MAX_FIDS} distinct fids")
+    if rc != 0:
+        raise RuntimeError(f"bcw_index_drop_fids: {L.lib.bcw_strerror(rc).decode()}")
+    out = FidUsageMap()
+    out.soft_deleted, out.invalid, out.overflow = int(res.soft_deleted), int(res.invalid), bool(res.overflow)
+    if not res.overflow:
+        assert res.fits, "the row buffer holds every row a drop can return"
+        for r in rows[:int(res.n_fids)]:
+            out[int(r.fid)] = FidUsage(int(r.count), int(r.bytes), int(r.span))
+    return out
 
 
 def freed_by_fid(index, n: int, d_found: int, d_free_fid: int, d_free_bytes: int, d_gate: int | None = None) -> dict:
@@ -116,5 +145,5 @@ def wal_garbage(index, wals) -> dict:
     return {fid: int(sz) - L.SUPER_BLOCK_SIZE - (use[fid].span if fid in use else 0) for fid, sz in sizes.items()}
 
 
-__all__ = ["FidUsage", "FidUsageMap", "PickerWalInfo", "fid_usage", "freed_by_fid", "default_compaction_picker",
-           "wal_garbage"]
+__all__ = ["FidUsage", "FidUsageMap", "PickerWalInfo", "fid_usage", "drop_fids", "freed_by_fid",
+           "default_compaction_picker", "wal_garbage"]

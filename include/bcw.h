@@ -832,6 +832,44 @@ int bcw_freed_by_fid_async(bcw_index* ix, uint64_t n, const uint8_t* d_found, co
                            const uint64_t* d_free_bytes, const bcw_write_result* d_gate, bcw_fid_usage* d_rows,
                            uint32_t cap, bcw_usage_result* d_res);
 
+/* ---- retiring WAL files from the index: drop entries by fid ---------------------------------------------------
+ * When a WAL file stops existing (compaction deletes its inputs once onePhase has re-put the surviving keys,
+ * compaction.go:256-285; reclaimDiskUsage deletes the oldest files outright, compaction.go:369-465) the entries that
+ * still point into it can never be read again: the keys the compaction filter dropped, and every key of a reclaimed
+ * file. The reference leaves them to its sampled eviction and answers ErrKeyNotFound for them (getWalRef(fid) == nil,
+ * db_impl.go:574-577). Here one pass over the slot table removes them: every live entry whose fid is in the list
+ * (BCW_DROP_IN: the files that were deleted) or is not in it (BCW_DROP_NOT_IN: keep only the files that exist)
+ * becomes what a Delete leaves -- not live, its slot and arena entry still claimed -- so `live` falls by the number
+ * dropped, slots_used does not change, and the next rebuild (bcw_index_compact, or a batch's own once half the
+ * claimed slots are dead) gives the space back. A soft-deleted entry (off == 0) names no file and is never dropped;
+ * every other live entry is selected by its fid alone, 0 < off < 40 included.
+ * Nothing a reference user can see changes: a Get of such a key is ErrKeyNotFound either way (BCW_GET_NO_WAL before,
+ * BCW_GET_NOT_FOUND after), and a later Put of it reports found = 0 where the reference reports the dead fid, which
+ * manifest.apply skips (manifest.go:506-512). The one deliberate difference: an index bounded by bcw_index_set_limit
+ * stops spending its bound on keys that cannot be read.
+ * h_fids: host array, any order, duplicates allowed, any uint64; copied before the call returns. More than
+ * BCW_USAGE_MAX_FIDS distinct fids, an unknown mode or a NULL list with n_fids > 0 is BCW_E_INVAL with the index
+ * untouched. n_fids == 0 drops nothing (BCW_DROP_IN) or every file-backed entry (BCW_DROP_NOT_IN).
+ * Output as bcw_index_fid_usage*: one row per fid that lost entries, ascending, by the same counting rule (an entry
+ * counts iff off >= 40; bytes its size; span WalRecordSize), so a BCW_DROP_IN call's rows are the rows
+ * bcw_index_fid_usage gave for those fids just before it. invalid: dropped entries with 0 < off < 40; soft_deleted:
+ * the soft-deleted entries the pass saw and kept. d_rows may be NULL with cap 0 (totals only). The drop is never
+ * partial: it depends neither on cap (fits == 0: no row written, totals and n_fids exact) nor on overflow (only
+ * BCW_DROP_NOT_IN with more than BCW_USAGE_MAX_FIDS distinct dead fids: everything selected is still dropped and
+ * `live` stays exact; only the rows and totals are void).
+ * Async form: d_rows / d_res are device pointers; runs on the index's context stream without synchronising, the
+ * index's buffers taken at launch (a drop queued after a batch sees the batch; a Put queued after the drop stays). One
+ * caller at a time on the index; the accounting scratch is the context's, so one accounting or drop call at a time
+ * per context. */
+#define BCW_DROP_IN      0   /* drop entries whose fid is in the list (files that were deleted) */
+#define BCW_DROP_NOT_IN  1   /* drop entries whose fid is not in the list (keep only the files that exist) */
+int bcw_index_drop_fids_async(bcw_index* ix, int mode, const uint64_t* h_fids, uint32_t n_fids,
+                              bcw_fid_usage* d_rows, uint32_t cap, bcw_usage_result* d_res);
+/* Synchronous, host out. Returns BCW_OK also when fits == 0 or overflow == 1: the drop has happened and cannot be
+ * retried, so both are left to the caller to read from h_res (rows are copied only when they were written). */
+int bcw_index_drop_fids(bcw_index* ix, int mode, const uint64_t* h_fids, uint32_t n_fids,
+                        bcw_fid_usage* h_rows, uint32_t cap, bcw_usage_result* h_res);
+
 /* ---- host I/O staging: WAL files <-> HBM through pinned slices ---------------------------------------
  * The reference reads a segment with PreadFull per 32 KiB block (utils.go:32-48, wal_iterator.go:55)
  * and writes the rewritten WAL through a buffer flushed every >= 1 MiB (WalRewriter
