@@ -1,7 +1,7 @@
 // bcw_crc_dev.h -- the device primitives the kernels that write or read framed WAL bytes share (bcw_encode.hip,
 // bcw_put.hip, bcw_read_body.h, bcw_index.hip): the CRC-32C tables a workgroup builds in LDS, the steps and shift
-// operators applied to a raw CRC state, the 16 B unit helpers of the copy loops and the wave-aggregated counter add.
-// The single home of each. What a kernel stages, its LDS layout and its launch bounds stay in the kernel.
+// operators applied to a raw CRC state, the 16 B unit helpers of the copy loops, the wave-aggregated counter add and
+// the wave sum. The single home of each. What a kernel stages, its LDS layout and its launch bounds stay in the kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -100,6 +100,12 @@ __device__ __forceinline__ uint64_t wave_alloc(uint64_t* ctr, uint64_t v) {
   if (lane == 63 && tot) base = atomicAdd(reinterpret_cast<unsigned long long*>(ctr), (unsigned long long)tot);
   base = __shfl(base, 63, 64);
   return base + incl - v;
+}
+// the sum of v over the wave's 64 lanes, in every lane (a butterfly: every lane of the wave calls it)
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
 }
 
 }  // namespace bcw

@@ -42,6 +42,7 @@
 #include "bcw_crc_dev.h"
 #include "bcw_drop.h"
 #include "bcw_internal.h"
+#include "bcw_murmur.h"
 #include "bcw_read_body.h"
 #include "bcw_rules.h"
 #include "bcw_usage.h"
@@ -67,6 +68,9 @@ constexpr uint64_t kProv = 1ull << 63;  // provisional slot reference (claim -> 
 // and its failure flag; k_ix_adopt makes them the index's once the rebuild is known to be whole
 enum { C_ARENA = 0, C_SLOTS = 1, C_LIVE = 2, C_OVERFLOW = 3, C_NIN = 4, C_DONE = 5, C_FAIL = 6, C_NEED = 7,
        C_EVICTED = 8, C_EVICTED_BYTES = 9, C_R_ARENA = 10, C_R_SLOTS = 11, C_R_FAIL = 12, C_NUM = 13 };
+// a call's own counters C_NIN .. C_FAIL and a rebuild's C_R_ARENA .. C_R_FAIL are each zeroed at once (zero_group)
+static_assert(C_DONE == C_NIN + 1 && C_FAIL == C_NIN + 2, "C_NIN, C_DONE, C_FAIL are adjacent");
+static_assert(C_R_SLOTS == C_R_ARENA + 1 && C_R_FAIL == C_R_ARENA + 2, "C_R_ARENA, C_R_SLOTS, C_R_FAIL are adjacent");
 
 // op sources
 // SRC_BATCH: a write batch (bcw_write_records*): flat merged keys as SRC_FLAT, but the number of ops is read from a
@@ -96,38 +100,6 @@ struct Src {
 };
 
 __device__ __forceinline__ bool flat_keys(const Src& s) { return s.kind == SRC_FLAT || s.kind == SRC_BATCH; }
-
-__device__ __forceinline__ uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-__device__ __forceinline__ uint64_t fmix64(uint64_t k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return k;
-}
-// MurmurHash3_x64_128 (seed 0) fed 16-byte blocks; Sum64 = h1
-struct Murmur {
-  uint64_t h1 = 0, h2 = 0;
-  __device__ __forceinline__ void block(uint64_t k1, uint64_t k2) {
-    const uint64_t c1 = 0x87c37b91114253d5ull, c2 = 0x4cf5ad432745937full;
-    k1 *= c1; k1 = rotl64(k1, 31); k1 *= c2; h1 ^= k1;
-    h1 = rotl64(h1, 27); h1 += h2; h1 = h1 * 5 + 0x52dce729;
-    k2 *= c2; k2 = rotl64(k2, 33); k2 *= c1; h2 ^= k2;
-    h2 = rotl64(h2, 31); h2 += h1; h2 = h2 * 5 + 0x38495ab5;
-  }
-  // tail of t = n & 15 bytes, zero-padded into k1 (bytes 0-7) and k2 (bytes 8-15)
-  __device__ __forceinline__ uint64_t finish(uint64_t k1, uint64_t k2, uint32_t t, uint64_t n) {
-    const uint64_t c1 = 0x87c37b91114253d5ull, c2 = 0x4cf5ad432745937full;
-    if (t > 8) { k2 *= c2; k2 = rotl64(k2, 33); k2 *= c1; h2 ^= k2; }
-    if (t > 0) { k1 *= c1; k1 = rotl64(k1, 31); k1 *= c2; h1 ^= k1; }
-    h1 ^= n; h2 ^= n;
-    h1 += h2; h2 += h1;
-    h1 = fmix64(h1); h2 = fmix64(h2);
-    h1 += h2;
-    return h1;
-  }
-};
 
 // 16 bytes of buf at signed offset a; bytes outside [0, n) read as 0
 __device__ __forceinline__ uint4 load16u(const uint8_t* __restrict__ buf, uint64_t n, int64_t a) {
@@ -248,7 +220,7 @@ __device__ __forceinline__ uint4 key_chunk(const Src& s, const Key& k, uint32_t 
 }
 
 __device__ __forceinline__ uint64_t key_hash(const Src& s, const Key& k) {
-  Murmur m;
+  murmur::State m;  // fed 16-byte blocks
   const uint32_t L = k.len(), nb = L / 16, t = L & 15u;
   for (uint32_t c = 0; c < nb; ++c) {
     const uint4 v = key_chunk(s, k, c);
@@ -272,6 +244,13 @@ __device__ __forceinline__ uint32_t table_fail(const bcw_decode_result* R, uint6
   return R->generation != gen ? BCW_ENC_ERR_STALE
          : (R->n_records > rows || R->err_class == BCW_ERR_INTERNAL) ? BCW_ENC_ERR_TABLE : 0u;
 }
+
+// An arena entry is a 16 B header {hash, key length, 0} and the key padded to 16 B (k_ix_commit lays it out):
+// the length word of the entry a slot's kref names, and the bytes an entry of a len-byte key takes
+__device__ __forceinline__ uint32_t entry_len(const uint8_t* __restrict__ arena, uint64_t kref) {
+  return *reinterpret_cast<const uint32_t*>(arena + (kref - 1) + 8);
+}
+__device__ __forceinline__ uint64_t entry_bytes(uint64_t len) { return 16ull + ((len + 15) & ~15ull); }
 
 // ---- batch launch 1: key hashes ----------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_ix_keys(Src s, uint64_t n, const bcw_decode_result* __restrict__ R,
@@ -390,7 +369,7 @@ __global__ __launch_bounds__(256) void k_ix_commit(Src s, uint64_t n, uint64_t* 
     own = sl != ~0ull && slots[sl].kref == (kProv | i);
     if (own) k = make_key(s, i);
   }
-  const uint64_t esz = own ? 16ull + (((uint64_t)k.len() + 15) & ~15ull) : 0;
+  const uint64_t esz = own ? entry_bytes(k.len()) : 0;
   const uint64_t a = wave_alloc(&cnt[C_ARENA], esz);
   if (!own) return;
   if (a + esz > arena_cap) {  // the host sizes the arena before the launch; never expected
@@ -414,7 +393,7 @@ __global__ __launch_bounds__(256) void k_ix_need(Src s, uint64_t rows, const bcw
   const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
   const uint64_t nin = table_fail(R, gen, rows) ? 0 : delivered_rows(R);
   uint64_t b = 0;
-  if (i < nin) b = 16ull + (((uint64_t)s.ns + s.t.key_len[i] + 15) & ~15ull);
+  if (i < nin) b = entry_bytes((uint64_t)s.ns + s.t.key_len[i]);
   (void)wave_alloc(&cnt[C_NEED], b);
 }
 
@@ -429,6 +408,12 @@ struct OpVals {
   uint64_t file_fid;
   int use_rec_fid;
 };
+
+// the op of record i of a write batch, from its BCW_WR_* flags (db_impl.go:441-448)
+__device__ __forceinline__ uint32_t batch_op(const Src& s, uint64_t i) {
+  const uint32_t fl = s.b_flags[i];
+  return (fl & BCW_WR_DELETED) ? BCW_IDX_DELETE : (fl & BCW_WR_TOMBSTONE) ? BCW_IDX_SOFT_DELETE : BCW_IDX_PUT;
+}
 
 __global__ __launch_bounds__(256) void k_ix_write(Src s, uint64_t n, uint64_t* __restrict__ cnt, OpVals v,
                                                   Slot* __restrict__ slots, const uint64_t* __restrict__ op_slot,
@@ -451,8 +436,7 @@ __global__ __launch_bounds__(256) void k_ix_write(Src s, uint64_t n, uint64_t* _
         off = v.off[i];
         size = v.size[i];
       } else if (s.kind == SRC_BATCH) {      // db_impl.go:441-448
-        const uint32_t fl = s.b_flags[i];
-        op = (fl & BCW_WR_DELETED) ? BCW_IDX_DELETE : (fl & BCW_WR_TOMBSTONE) ? BCW_IDX_SOFT_DELETE : BCW_IDX_PUT;
+        op = batch_op(s, i);
         fid = s.b_fid;
         off = s.b_off[i];
         size = s.b_size[i];
@@ -490,10 +474,6 @@ __global__ __launch_bounds__(256) void k_ix_write(Src s, uint64_t n, uint64_t* _
 // round trip). The ops of one key are those of one slot: k_put_link chains them through the slot's spare word (an
 // unordered list: link[i] = the previous head), k_put_stat walks its key's list for the latest op before its own (the
 // list is as long as the key's ops in this batch), k_put_unlink clears the word again.
-__device__ __forceinline__ uint32_t batch_op(const Src& s, uint64_t i) {
-  const uint32_t fl = s.b_flags[i];
-  return (fl & BCW_WR_DELETED) ? BCW_IDX_DELETE : (fl & BCW_WR_TOMBSTONE) ? BCW_IDX_SOFT_DELETE : BCW_IDX_PUT;
-}
 __global__ __launch_bounds__(256) void k_put_link(const uint64_t* __restrict__ cnt, Slot* __restrict__ slots,
                                                   const uint64_t* __restrict__ op_slot, uint64_t* __restrict__ link) {
   const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
@@ -537,9 +517,11 @@ __global__ void k_put_idx_err(const uint64_t* __restrict__ cnt, int32_t* __restr
 }
 
 // ---- lookups -----------------------------------------------------------------------------------------
-// the slot holding op i's key, or ~0
-__device__ __forceinline__ uint64_t find_slot(const Src& s, const Key& k, uint64_t h, const Slot* __restrict__ slots,
+// hash, probe, compare: the slot holding key k, or ~0. A lookup (Index.Get, index.go:81-98) is this and the slot's
+// `live`; its callers spell that test out, because a helper that returns "found" made their kernels longer.
+__device__ __forceinline__ uint64_t find_slot(const Src& s, const Key& k, const Slot* __restrict__ slots,
                                               uint64_t mask, const uint8_t* __restrict__ arena) {
+  const uint64_t h = key_hash(s, k);
   const uint32_t L = k.len();
   uint64_t j = h & mask;
   for (uint64_t probe = 0; probe <= mask; ++probe, j = (j + 1) & mask) {
@@ -548,6 +530,7 @@ __device__ __forceinline__ uint64_t find_slot(const Src& s, const Key& k, uint64
     if (slots[j].hash != h) continue;
     const uint4 hd = *reinterpret_cast<const uint4*>(arena + (kr - 1));
     if (hd.z != L) continue;
+    // arena_matches' compare, written out: calling it here was tried and made every lookup kernel's body longer
     const uint4* q = reinterpret_cast<const uint4*>(arena + (kr - 1) + 16);
     bool eq = true;
     for (uint32_t c = 0; c < (L + 15) / 16 && eq; ++c) {
@@ -567,8 +550,7 @@ __global__ __launch_bounds__(256) void k_ix_get(Src s, uint64_t n, const Slot* _
   const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
   if (i >= n) return;
   const Key k = make_key(s, i);
-  const uint64_t h = key_hash(s, k);
-  const uint64_t j = find_slot(s, k, h, slots, mask, arena);
+  const uint64_t j = find_slot(s, k, slots, mask, arena);
   uint8_t st = BCW_IDX_NOT_FOUND;
   uint64_t f = 0, o = 0, z = 0;
   if (j != ~0ull && slots[j].live) {
@@ -597,8 +579,7 @@ __global__ __launch_bounds__(kGetLookupKeys) void k_get_lookup(Src s, GetLookup 
   if (i < g.n) {
     s.keys_len = s.koff[g.n];
     const Key k = make_key(s, i);
-    const uint64_t h = key_hash(s, k);
-    const uint64_t j = find_slot(s, k, h, slots, mask, arena);
+    const uint64_t j = find_slot(s, k, slots, mask, arena);
     uint8_t gs = BCW_GET_NOT_FOUND, rs = BCW_RD_OK;
     uint64_t f = 0, o = 0, z = 0;
     if (j != ~0ull && slots[j].live) {
@@ -639,7 +620,7 @@ __global__ __launch_bounds__(kGetLookupKeys) void k_get_lookup(Src s, GetLookup 
   }
   uint64_t sum = slot, nf = found;
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
+  for (int d = 32; d >= 1; d >>= 1) {  // two wave_sums, interleaved: one after the other waits twice as often
     sum += __shfl_xor(sum, d, 64);
     nf += __shfl_xor(nf, d, 64);
   }
@@ -656,38 +637,74 @@ __global__ __launch_bounds__(kGetLookupKeys) void k_get_lookup(Src s, GetLookup 
 // compactOneWal's doFilter (compaction.go:329-348, without the user CompactionFilter) of every delivered
 // row of a decoded data WAL: keep = Get succeeds (not deleted / soft-deleted) and still points at
 // (src fid, foff - 7) (compaction.go:302); rows the iteration does not deliver get 0
-__global__ __launch_bounds__(256) void k_ix_filter(Src s, uint64_t rows, const bcw_decode_result* __restrict__ R,
-                                                   uint64_t gen, const Slot* __restrict__ slots, uint64_t mask,
-                                                   const uint8_t* __restrict__ arena, uint64_t src_fid,
-                                                   uint8_t* __restrict__ keep, uint64_t* __restrict__ cnt) {
-  const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
-  const uint32_t fail = table_fail(R, gen, rows);
-  const uint64_t nin = fail ? 0 : delivered_rows(R);
-  if (i == 0) { cnt[C_NIN] = nin; cnt[C_FAIL] = fail; }
-  uint8_t kp = 0;
-  if (i < nin) {
-    const Key k = make_key(s, i);
-    const uint64_t h = key_hash(s, k);
-    const uint64_t j = find_slot(s, k, h, slots, mask, arena);
-    if (j != ~0ull && slots[j].live && slots[j].off != 0)
-      kp = (slots[j].fid == src_fid && slots[j].off == s.t.foff[i] - kHdr) ? 1 : 0;
-  }
-  if (i < rows) keep[i] = kp;
-  (void)wave_alloc(&cnt[C_DONE], kp ? 1ull : 0ull);
-}
-
-// k_ix_filter with the index's compaction filter rules (bcw_index_set_compact_rules, bcw_rules.h): the same index
+//
+// With the index's compaction filter rules (bcw_index_set_compact_rules, bcw_rules.h; kRules): the same index
 // check first, then, only for a row that is still kept, the rules in their order -- the two column rules from the
 // table's expire / flags, the prefix rule over the merged key's first 16 B chunks (key_chunk, as the lookup reads
-// them: a namespace or key that straddles fragments takes its slow path) against the prefix table, which the workgroup
-// stages into LDS once. A row counts for the first rule that matches it (one wave-aggregated add per rule and wave).
-// Launched only when rules are set: with none, the filter is k_ix_filter above.
+// them: a namespace or key that straddles fragments takes its slow path) against the prefix table pt, which the
+// workgroup has staged into LDS. A row counts for the first rule that matches it (one wave-aggregated add per rule and
+// wave). One text, two kernels: k_ix_filter compiles none of the rules, k_ix_filter_rules is launched only when rules
+// are set.
 struct Rules {
   uint32_t mask, n_prefix, longest;  // n_prefix: 0 unless BCW_RULE_PREFIX is set
   uint64_t now;
   const rules::PrefixTable* table;   // device
   uint64_t* cnt;                     // device: rows dropped by {expired, tombstone, prefix}
 };
+
+template <bool kRules>
+__device__ __forceinline__ void filter_rows(const Src& s, uint64_t rows, const bcw_decode_result* __restrict__ R,
+                                            uint64_t gen, const Slot* __restrict__ slots, uint64_t mask,
+                                            const uint8_t* __restrict__ arena, uint64_t src_fid,
+                                            uint8_t* __restrict__ keep, uint64_t* __restrict__ cnt, const Rules& ru,
+                                            const rules::PrefixTable* pt) {
+  const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
+  const uint32_t fail = table_fail(R, gen, rows);
+  const uint64_t nin = fail ? 0 : delivered_rows(R);
+  if (i == 0) { cnt[C_NIN] = nin; cnt[C_FAIL] = fail; }
+  uint8_t kp = 0;
+  uint32_t hit = rules::kNone;
+  if (i < nin) {
+    const Key k = make_key(s, i);
+    const uint64_t j = find_slot(s, k, slots, mask, arena);
+    if (j != ~0ull && slots[j].live && slots[j].off != 0)
+      kp = (slots[j].fid == src_fid && slots[j].off == s.t.foff[i] - kHdr) ? 1 : 0;
+    if constexpr (kRules) {
+      if (kp) {
+        hit = rules::first_match(ru.mask, ru.now, s.t.expire[i], s.t.flags[i], k.len(), pt->w, pt->len, ru.n_prefix,
+                                 ru.longest, [&](uint32_t* kw, uint32_t n) {
+#pragma unroll
+                                   for (uint32_t c = 0; c < rules::kKeyChunks; ++c) {
+                                     if (c >= n) break;
+                                     const uint4 x = key_chunk(s, k, c);
+                                     kw[4 * c] = x.x;
+                                     kw[4 * c + 1] = x.y;
+                                     kw[4 * c + 2] = x.z;
+                                     kw[4 * c + 3] = x.w;
+                                   }
+                                 });
+        if (hit != rules::kNone) kp = 0;
+      }
+    }
+  }
+  if (i < rows) keep[i] = kp;
+  (void)wave_alloc(&cnt[C_DONE], kp ? 1ull : 0ull);
+  if constexpr (kRules) {
+#pragma unroll
+    for (uint32_t r = rules::kExpired; r <= rules::kPrefix; ++r) {
+      const uint64_t b = __ballot(hit == r);
+      if ((threadIdx.x & 63u) == 0 && b)
+        atomicAdd(reinterpret_cast<unsigned long long*>(&ru.cnt[r - 1]), (unsigned long long)__popcll(b));
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ix_filter(Src s, uint64_t rows, const bcw_decode_result* __restrict__ R,
+                                                   uint64_t gen, const Slot* __restrict__ slots, uint64_t mask,
+                                                   const uint8_t* __restrict__ arena, uint64_t src_fid,
+                                                   uint8_t* __restrict__ keep, uint64_t* __restrict__ cnt) {
+  filter_rows<false>(s, rows, R, gen, slots, mask, arena, src_fid, keep, cnt, Rules{}, nullptr);
+}
 
 __global__ __launch_bounds__(256) void k_ix_filter_rules(Src s, uint64_t rows, const bcw_decode_result* __restrict__ R,
                                                          uint64_t gen, const Slot* __restrict__ slots, uint64_t mask,
@@ -702,42 +719,7 @@ __global__ __launch_bounds__(256) void k_ix_filter_rules(Src s, uint64_t rows, c
     if (threadIdx.x < ru.n_prefix) pt.len[threadIdx.x] = ru.table->len[threadIdx.x];
   }
   __syncthreads();
-  const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
-  const uint32_t fail = table_fail(R, gen, rows);
-  const uint64_t nin = fail ? 0 : delivered_rows(R);
-  if (i == 0) { cnt[C_NIN] = nin; cnt[C_FAIL] = fail; }
-  uint8_t kp = 0;
-  uint32_t hit = rules::kNone;
-  if (i < nin) {
-    const Key k = make_key(s, i);
-    const uint64_t h = key_hash(s, k);
-    const uint64_t j = find_slot(s, k, h, slots, mask, arena);
-    if (j != ~0ull && slots[j].live && slots[j].off != 0)
-      kp = (slots[j].fid == src_fid && slots[j].off == s.t.foff[i] - kHdr) ? 1 : 0;
-    if (kp) {
-      hit = rules::first_match(ru.mask, ru.now, s.t.expire[i], s.t.flags[i], k.len(), pt.w, pt.len, ru.n_prefix,
-                               ru.longest, [&](uint32_t* kw, uint32_t n) {
-#pragma unroll
-                                 for (uint32_t c = 0; c < rules::kKeyChunks; ++c) {
-                                   if (c >= n) break;
-                                   const uint4 v = key_chunk(s, k, c);
-                                   kw[4 * c] = v.x;
-                                   kw[4 * c + 1] = v.y;
-                                   kw[4 * c + 2] = v.z;
-                                   kw[4 * c + 3] = v.w;
-                                 }
-                               });
-      if (hit != rules::kNone) kp = 0;
-    }
-  }
-  if (i < rows) keep[i] = kp;
-  (void)wave_alloc(&cnt[C_DONE], kp ? 1ull : 0ull);
-#pragma unroll
-  for (uint32_t r = rules::kExpired; r <= rules::kPrefix; ++r) {
-    const uint64_t b = __ballot(hit == r);
-    if ((threadIdx.x & 63u) == 0 && b)
-      atomicAdd(reinterpret_cast<unsigned long long*>(&ru.cnt[r - 1]), (unsigned long long)__popcll(b));
-  }
+  filter_rows<true>(s, rows, R, gen, slots, mask, arena, src_fid, keep, cnt, ru, &pt);
 }
 
 // the rule counts of a synchronous compaction whose output is final join the cumulative ones (rule counters:
@@ -759,24 +741,32 @@ __global__ void k_ix_result(const uint64_t* __restrict__ cnt, bcw_index_result* 
 }
 
 // ---- growth: re-insert every claimed slot into a larger table ---------------------------------------
+// slot S of an old table into the first empty slot of the fresh table nw from its hash, under the reference kref and
+// the presence `live`; false: no empty slot
+__device__ __forceinline__ bool insert_slot(Slot* __restrict__ nw, uint64_t mask, const Slot& S, uint64_t kref,
+                                            uint64_t live) {
+  uint64_t j = S.hash & mask;
+  for (uint64_t probe = 0; probe <= mask; ++probe, j = (j + 1) & mask) {
+    if (atomicCAS(reinterpret_cast<unsigned long long*>(&nw[j].kref), 0ull, (unsigned long long)kref) == 0) {
+      nw[j].seq = S.seq;
+      nw[j].hash = S.hash;
+      nw[j].fid = S.fid;
+      nw[j].off = S.off;
+      nw[j].size = S.size;
+      nw[j].live = live;
+      return true;
+    }
+  }
+  return false;
+}
+
 __global__ __launch_bounds__(256) void k_ix_rehash(const Slot* __restrict__ old, uint64_t old_cap,
                                                    Slot* __restrict__ nw, uint64_t mask) {
   const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
   if (i >= old_cap) return;
   const Slot S = old[i];
   if (S.kref == 0) return;
-  uint64_t j = S.hash & mask;
-  for (uint64_t probe = 0; probe <= mask; ++probe, j = (j + 1) & mask) {
-    if (atomicCAS(reinterpret_cast<unsigned long long*>(&nw[j].kref), 0ull, (unsigned long long)S.kref) == 0) {
-      nw[j].seq = S.seq;
-      nw[j].hash = S.hash;
-      nw[j].fid = S.fid;
-      nw[j].off = S.off;
-      nw[j].size = S.size;
-      nw[j].live = S.live;
-      return;
-    }
-  }
+  (void)insert_slot(nw, mask, S, S.kref, S.live);  // the larger table has room
 }
 
 // ---- reclaim: rebuild the table and the arena from the live keys only ---------------------------------
@@ -795,8 +785,8 @@ __global__ __launch_bounds__(256) void k_ix_live_bytes(const Slot* __restrict__ 
   const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
   uint64_t b = 0;
   if (i < cap && slots[i].kref && slots[i].live && slots[i].kref - 1 + 16 <= arena_cap)
-    b = 16ull + (((uint64_t)*reinterpret_cast<const uint32_t*>(arena + (slots[i].kref - 1) + 8) + 15) & ~15ull);
-  for (int d = 32; d >= 1; d >>= 1) b += __shfl_xor(b, d, 64);
+    b = entry_bytes(entry_len(arena, slots[i].kref));
+  b = wave_sum(b);
   if ((threadIdx.x & 63u) == 0 && b) atomicAdd(reinterpret_cast<unsigned long long*>(out), (unsigned long long)b);
 }
 
@@ -814,7 +804,7 @@ __global__ __launch_bounds__(256) void k_ix_compact(const Slot* __restrict__ old
     const uint64_t src = S.kref - 1;
     bool in = (S.kref & kProv) == 0 && (src & 15u) == 0 && src + 16 <= old_arena_cap;
     if (in) {
-      esz = 16ull + (((uint64_t)*reinterpret_cast<const uint32_t*>(old_arena + src + 8) + 15) & ~15ull);
+      esz = entry_bytes(entry_len(old_arena, S.kref));
       in = src + esz <= old_arena_cap;
     }
     if (!in) {
@@ -833,19 +823,8 @@ __global__ __launch_bounds__(256) void k_ix_compact(const Slot* __restrict__ old
   const uint4* __restrict__ s = reinterpret_cast<const uint4*>(old_arena + (S.kref - 1));
   uint4* __restrict__ d = reinterpret_cast<uint4*>(arena + a);
   for (uint64_t c = 0; c < esz / 16; ++c) d[c] = s[c];
-  uint64_t j = S.hash & mask;
-  for (uint64_t probe = 0; probe <= mask; ++probe, j = (j + 1) & mask) {
-    if (atomicCAS(reinterpret_cast<unsigned long long*>(&nw[j].kref), 0ull, (unsigned long long)(a + 1)) == 0) {
-      nw[j].seq = S.seq;
-      nw[j].hash = S.hash;
-      nw[j].fid = S.fid;
-      nw[j].off = S.off;
-      nw[j].size = S.size;
-      nw[j].live = 1;
-      return;
-    }
-  }
-  atomicOr(reinterpret_cast<unsigned long long*>(&cnt[C_R_FAIL]), 2ull);  // no empty slot; never expected
+  if (!insert_slot(nw, mask, S, a + 1, 1))
+    atomicOr(reinterpret_cast<unsigned long long*>(&cnt[C_R_FAIL]), 2ull);  // no empty slot; never expected
 }
 
 // the rebuilt table's counters become the index's: every claimed slot is live
@@ -859,20 +838,22 @@ __global__ void k_ix_adopt(uint64_t* __restrict__ cnt) {
 // fids (sorted, nf > 0): only entries whose value fid is one of them (the slice of the index that points into
 // a set of WAL files: the compaction fan-out's filter snapshot); nf == 0: every entry. The membership test is
 // bcw_drop.h's.
+__device__ __forceinline__ bool slot_exported(const Slot& S, const uint64_t* __restrict__ fids, uint32_t nf) {
+  return S.kref && S.live && (nf == 0 || drop::fid_in(fids, nf, S.fid));
+}
+
 __global__ __launch_bounds__(256) void k_ix_count(const Slot* __restrict__ slots, uint64_t cap,
                                                   const uint8_t* __restrict__ arena, const uint64_t* __restrict__ fids,
                                                   uint32_t nf, uint64_t* __restrict__ blk_n,
                                                   uint64_t* __restrict__ blk_b) {
   const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
   uint64_t c = 0, b = 0;
-  if (i < cap && slots[i].kref && slots[i].live && (nf == 0 || drop::fid_in(fids, nf, slots[i].fid))) {
+  if (i < cap && slot_exported(slots[i], fids, nf)) {
     c = 1;
-    b = *reinterpret_cast<const uint32_t*>(arena + (slots[i].kref - 1) + 8);
+    b = entry_len(arena, slots[i].kref);
   }
-  for (int d = 32; d >= 1; d >>= 1) {
-    c += __shfl_xor(c, d, 64);
-    b += __shfl_xor(b, d, 64);
-  }
+  c = wave_sum(c);
+  b = wave_sum(b);
   __shared__ uint64_t sc[4], sb[4];
   if ((threadIdx.x & 63) == 0) { sc[threadIdx.x >> 6] = c; sb[threadIdx.x >> 6] = b; }
   __syncthreads();
@@ -892,10 +873,10 @@ __global__ __launch_bounds__(256) void k_ix_export(const Slot* __restrict__ slot
   uint64_t c = 0, b = 0;
   Slot S{};
   if (i < cap) S = slots[i];
-  const bool act = i < cap && S.kref && S.live && (nf == 0 || drop::fid_in(fids, nf, S.fid));
+  const bool act = i < cap && slot_exported(S, fids, nf);
   if (act) {
     c = 1;
-    b = *reinterpret_cast<const uint32_t*>(arena + (S.kref - 1) + 8);
+    b = entry_len(arena, S.kref);
   }
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   uint64_t ic = c, ib = b;
@@ -1154,15 +1135,24 @@ struct bcw_index {
   hipEvent_t drop_ev = nullptr;
 };
 
+namespace {
+// flat merged keys on the device: key i = keys[koff[i], koff[i + 1])
+Src flat_src(const uint8_t* keys, const uint64_t* koff, uint64_t keys_len) {
+  Src s{};
+  s.kind = SRC_FLAT;
+  s.keys = keys;
+  s.koff = koff;
+  s.keys_len = keys_len;
+  return s;
+}
+}  // namespace
+
 namespace bcw {
 bcw_ctx* index_ctx(const bcw_index* ix) { return ix ? ix->ctx : nullptr; }
 
 hipError_t ix_launch_get_lookup(bcw_index* x, const GetLookup& g, hipStream_t st) {
   if (g.n == 0) return hipSuccess;
-  Src s{};
-  s.kind = SRC_FLAT;
-  s.keys = g.keys;
-  s.koff = g.koff;  // keys_len: the kernel reads koff[n]
+  const Src s = flat_src(g.keys, g.koff, 0);  // keys_len: the kernel reads koff[n]
   k_get_lookup<<<(uint32_t)((g.n + kGetLookupKeys - 1) / kGetLookupKeys), kGetLookupKeys, 0, st>>>(
       s, g, x->slots, x->cap - 1, x->arena);
   return hipGetLastError();
@@ -1185,6 +1175,15 @@ int ix_sync_counters(bcw_index* x, uint64_t* out) {
     return BCW_E_HIP;
   return BCW_OK;
 }
+
+// the host's upper bounds, made exact from counters just read (c: ix_sync_counters)
+void ix_refresh_bounds(bcw_index* x, const uint64_t* c) {
+  x->slots_ub = c[C_SLOTS];
+  x->arena_ub = c[C_ARENA];
+}
+
+// three adjacent counters from `first` (cnt + C_NIN, cnt + C_R_ARENA, or the rules' three) to zero
+hipError_t zero_group(uint64_t* first, hipStream_t st) { return hipMemsetAsync(first, 0, 3 * sizeof(uint64_t), st); }
 
 // grow the slot table to hold `slots` claimed slots at kMaxLoad and the arena to `arena` bytes
 int ix_grow(bcw_index* x, uint64_t slots, uint64_t arena) {
@@ -1232,7 +1231,7 @@ int ix_compact(bcw_index* x, uint64_t ncap, uint64_t narena) {
   }
   uint64_t c[C_NUM];
   bool ok = hipMemsetAsync(ns, 0, ncap * sizeof(Slot), st) == hipSuccess &&
-            hipMemsetAsync(x->cnt + C_R_ARENA, 0, 3 * sizeof(uint64_t), st) == hipSuccess;  // C_R_ARENA, _SLOTS, _FAIL
+            zero_group(x->cnt + C_R_ARENA, st) == hipSuccess;
   if (ok)
     k_ix_compact<<<(uint32_t)((x->cap + 255) / 256), 256, 0, st>>>(x->slots, x->cap, x->arena, x->arena_cap, ns,
                                                                    ncap - 1, na, narena, x->cnt);
@@ -1271,8 +1270,7 @@ int ix_room(bcw_index* x, uint64_t n, uint64_t arena_bytes) {
     int rc = ix_sync_counters(x, c);
     if (rc != BCW_OK) return rc;
     if (c[C_OVERFLOW]) return BCW_E_CAPACITY;  // a previous batch overflowed: the index is inconsistent
-    x->slots_ub = c[C_SLOTS];
-    x->arena_ub = c[C_ARENA];
+    ix_refresh_bounds(x, c);
     if (c[C_SLOTS] > 0 && c[C_SLOTS] - c[C_LIVE] >= c[C_SLOTS] / 2) {
       rc = ix_compact(x, x->cap, x->arena_cap);
       if (rc != BCW_OK) return rc;
@@ -1311,6 +1309,38 @@ int ix_stage(bcw_index* x, uint64_t bytes) {
   return BCW_OK;
 }
 
+// The flat keys of a host call, key i = h_keys[h_key_off[i], h_key_off[i + 1]), n > 0: flat_keys_ok refuses offsets
+// that run backwards and a NULL h_keys with key bytes; stage_flat_keys sizes x->stage for keys | offsets rebased to
+// the first key | `rest` bytes of the caller's own, and queues the copies of the first two.
+struct FlatStage {
+  Src src;                     // the staged keys
+  uint8_t* rest;               // device, 8-byte aligned: the caller's part of the staging buffer
+  std::vector<uint64_t> koff;  // the rebased offsets the copy reads: alive until the caller has synchronised
+};
+int flat_keys_ok(uint64_t n, const uint8_t* h_keys, const uint64_t* h_key_off) {
+  if (h_key_off[n] != h_key_off[0] && !h_keys) return BCW_E_INVAL;
+  for (uint64_t i = 0; i < n; ++i)
+    if (h_key_off[i + 1] < h_key_off[i]) return BCW_E_INVAL;
+  return BCW_OK;
+}
+int stage_flat_keys(bcw_index* x, uint64_t n, const uint8_t* h_keys, const uint64_t* h_key_off, uint64_t rest,
+                    FlatStage* f) {
+  const uint64_t kb = h_key_off[n] - h_key_off[0], kbp = (kb + 15) & ~15ull;
+  const int rc = ix_stage(x, kbp + 8 * (n + 1) + rest + 64);
+  if (rc != BCW_OK) return rc;
+  uint8_t* d_keys = (uint8_t*)x->stage;
+  uint64_t* d_koff = (uint64_t*)(d_keys + kbp);
+  hipStream_t st = x->ctx->cur;
+  f->koff.resize(n + 1);
+  for (uint64_t i = 0; i <= n; ++i) f->koff[i] = h_key_off[i] - h_key_off[0];
+  if ((kb && hipMemcpyAsync(d_keys, h_keys + h_key_off[0], kb, hipMemcpyHostToDevice, st) != hipSuccess) ||
+      hipMemcpyAsync(d_koff, f->koff.data(), 8 * (n + 1), hipMemcpyHostToDevice, st) != hipSuccess)
+    return BCW_E_HIP;
+  f->src = flat_src(d_keys, d_koff, kb);
+  f->rest = (uint8_t*)(d_koff + (n + 1));
+  return BCW_OK;
+}
+
 // the capacity bound after a batch (k_ix_evict), when one is set
 void ix_bound(bcw_index* x) {
   if (!x->limited) return;
@@ -1324,7 +1354,7 @@ void ix_batch(bcw_index* x, const Src& s, uint64_t n, const bcw_decode_result* R
               uint8_t* old_found = nullptr, uint64_t* old_fid = nullptr, uint64_t* old_size = nullptr) {
   hipStream_t st = x->ctx->cur;
   const uint32_t grid = (uint32_t)((n + 255) / 256);
-  (void)hipMemsetAsync(x->cnt + C_NIN, 0, 3 * sizeof(uint64_t), st);  // C_NIN, C_DONE, C_FAIL
+  (void)zero_group(x->cnt + C_NIN, st);
   if (!grid) return;
   k_ix_keys<<<grid, 256, 0, st>>>(s, n, R, gen, x->cnt, x->op_kref, x->op_hash);
   k_ix_claim<<<grid, 256, 0, st>>>(s, n, x->cnt, x->slots, x->cap - 1, x->arena, x->cnt, x->op_kref, x->op_hash,
@@ -1347,6 +1377,12 @@ Src table_src(bcw_ctx* c, const uint8_t* d_seg, const bcw_decode_params* p, cons
   s.ns = p->ns_size;
   return s;
 }
+// c's latest decode left a fragment table, and the table has the columns every table source reads (need_size: and
+// the one the index rebuild takes its values from)
+bool table_ok(const bcw_ctx* c, const bcw_record_table* t, bool need_size) {
+  return c->s.frags && t->foff && (!need_size || t->size) && t->key_len && t->first_frag && t->emit_frag &&
+         t->hdr_size;
+}
 
 // doFilter of every row of a decoded table on stream st, counters in cnt: with no rules set the filter without
 // rules (k_ix_filter, as it always was), else the rules variant, which counts the rows each rule drops into
@@ -1366,6 +1402,76 @@ int ix_launch_filter(bcw_index* x, const Src& s, uint64_t rows, const bcw_decode
   k_ix_filter_rules<<<grid, 256, 0, st>>>(s, rows, d_result, gen, x->slots, x->cap - 1, x->arena, src_fid, d_keep, cnt,
                                           ru);
   return BCW_OK;
+}
+
+// The one filter call behind ix_filter_on, ix_filter_pending and bcw_compact_filter_async: c is the context whose
+// decode made the table and whose stream runs the filter, cnt the counter block the call counts in (the index's own,
+// or a caller's, which first takes a copy of the index's, its overflow flag included), rule_cnt the three words the
+// rules count in, zeroed first when the call owns them (zero_rules).
+int ix_filter(bcw_index* x, bcw_ctx* c, const uint8_t* d_seg, const bcw_decode_params* p,
+              const bcw_record_table* d_table, const bcw_decode_result* d_result, uint64_t src_fid, uint8_t* d_keep,
+              uint64_t* cnt, uint64_t* rule_cnt, bool zero_rules, bcw_index_result* d_out) {
+  if (!p || !d_table || !d_result || !d_keep || p->mode != BCW_MODE_RECORD || !table_ok(c, d_table, false))
+    return BCW_E_INVAL;
+  DeviceGuard dg(c->device);
+  if (!dg.ok) return BCW_E_HIP;
+  hipStream_t st = c->cur;
+  if (cnt != x->cnt) (void)hipMemcpyAsync(cnt, x->cnt, C_NUM * sizeof(uint64_t), hipMemcpyDeviceToDevice, st);
+  (void)zero_group(cnt + C_NIN, st);
+  if (zero_rules) (void)zero_group(rule_cnt, st);
+  const Src s = table_src(c, d_seg, p, d_table, SRC_RECORD);
+  const int rc =
+      ix_launch_filter(x, s, d_table->capacity, d_result, c->frag_gen, src_fid, d_keep, cnt, rule_cnt, st);
+  if (rc != BCW_OK) return rc;
+  if (d_out) k_ix_result<<<1, 1, 0, st>>>(cnt, d_out);
+  return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
+}
+
+// A usage-shaped pass over the slot table (k_ix_usage, k_ix_drop) on stream st: launch(grid) queues the kernel. The
+// buffers are taken as they are now: a batch queued before this call has already grown them.
+template <class Launch>
+int ix_usage_pass(bcw_index* x, int kid, hipStream_t st, Launch&& launch) {
+  if (!x->slots || !x->cap) return BCW_OK;
+  bcw_ctx* c = x->ctx;
+  const uint64_t wgs = (x->cap + kUsageSlots - 1) / kUsageSlots;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(wgs, (uint64_t)c->num_cus * 8);
+  hipEvent_t ev = nullptr;
+  c->prof.begin(kid, st, ev);
+  launch(grid);
+  c->prof.end(kid, st, ev);
+  return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
+}
+
+// The synchronous form of bcw_index_fid_usage_async / bcw_index_drop_fids_async: one device allocation for the
+// result and cap rows, async(d_rows, d_res), the result read back, then the rows when they are whole. must_fit: rows
+// that are not whole (fits == 0, or an overflow) are BCW_E_CAPACITY; otherwise they are the caller's to read.
+template <class Async>
+int ix_usage_sync(bcw_index* x, bcw_fid_usage* h_rows, uint32_t cap, bcw_usage_result* h_res, bool must_fit,
+                  Async&& async) {
+  if (!x || !h_res || (cap && !h_rows)) return BCW_E_INVAL;
+  bcw_ctx* c = x->ctx;
+  DeviceGuard dg(c->device);
+  if (!dg.ok) return BCW_E_HIP;
+  void* mem = nullptr;
+  if (hipMalloc(&mem, sizeof(bcw_usage_result) + (uint64_t)cap * sizeof(bcw_fid_usage)) != hipSuccess)
+    return BCW_E_NOMEM;
+  bcw_usage_result* d_res = static_cast<bcw_usage_result*>(mem);
+  bcw_fid_usage* d_rows = cap ? reinterpret_cast<bcw_fid_usage*>(d_res + 1) : nullptr;
+  int rc = async(d_rows, d_res);
+  if (rc == BCW_OK &&
+      (hipMemcpyAsync(h_res, d_res, sizeof *h_res, hipMemcpyDeviceToHost, c->cur) != hipSuccess ||
+       hipStreamSynchronize(c->cur) != hipSuccess))
+    rc = BCW_E_HIP;
+  const bool whole = rc == BCW_OK && h_res->fits && !h_res->overflow;
+  if (rc == BCW_OK && !whole && must_fit) rc = BCW_E_CAPACITY;
+  if (whole && h_res->n_fids &&
+      (hipMemcpyAsync(h_rows, d_rows, h_res->n_fids * sizeof(bcw_fid_usage), hipMemcpyDeviceToHost, c->cur) !=
+           hipSuccess ||
+       hipStreamSynchronize(c->cur) != hipSuccess))
+    rc = BCW_E_HIP;
+  (void)hipStreamSynchronize(c->cur);
+  (void)hipFree(mem);
+  return rc;
 }
 
 }  // namespace
@@ -1474,25 +1580,10 @@ int ix_filter_on(bcw_index* x, bcw_ctx* c, const uint8_t* d_seg, const bcw_decod
                  uint64_t* d_cnt, bcw_index_result* d_out) {
   static_assert(C_NUM <= kIxRuleCnt && kIxRuleCnt + 3 <= kIxCounters,
                 "the per-call counters hold every index counter and the three rule counts");
-  if (!x || !c || !p || !d_table || !d_result || !d_keep || !d_cnt || p->mode != BCW_MODE_RECORD ||
-      c->device != x->ctx->device)
-    return BCW_E_INVAL;
-  if (!c->s.frags || !d_table->foff || !d_table->key_len || !d_table->first_frag || !d_table->emit_frag ||
-      !d_table->hdr_size)
-    return BCW_E_INVAL;
-  DeviceGuard dg(c->device);
-  if (!dg.ok) return BCW_E_HIP;
-  const uint64_t rows = d_table->capacity;
-  hipStream_t st = c->cur;
-  // the index's counters (its overflow flag included), then this call's own zeroed
-  (void)hipMemcpyAsync(d_cnt, x->cnt, C_NUM * sizeof(uint64_t), hipMemcpyDeviceToDevice, st);
-  (void)hipMemsetAsync(d_cnt + C_NIN, 0, 3 * sizeof(uint64_t), st);
-  if (x->rules.mask) (void)hipMemsetAsync(d_cnt + kIxRuleCnt, 0, 3 * sizeof(uint64_t), st);  // this call's counts
-  const Src s = table_src(c, d_seg, p, d_table, SRC_RECORD);
-  const int rc = ix_launch_filter(x, s, rows, d_result, c->frag_gen, src_fid, d_keep, d_cnt, d_cnt + kIxRuleCnt, st);
-  if (rc != BCW_OK) return rc;
-  if (d_out) k_ix_result<<<1, 1, 0, st>>>(d_cnt, d_out);
-  return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
+  if (!x || !c || !d_cnt || c->device != x->ctx->device) return BCW_E_INVAL;
+  // the index's counters, then this call's own zeroed; the rule counts of this call alone
+  return ix_filter(x, c, d_seg, p, d_table, d_result, src_fid, d_keep, d_cnt, d_cnt + kIxRuleCnt, x->rules.mask != 0,
+                   d_out);
 }
 
 bool ix_has_rules(const bcw_index* x) { return x->rules.mask != 0; }
@@ -1514,38 +1605,14 @@ int ix_rule_commit(bcw_index* x) {
 }
 }  // namespace bcw
 
-namespace {
-// bcw_compact_filter_async; pending: the rows the rules drop are counted apart, for ix_rule_commit
-int ix_filter_own(bcw_index* x, const uint8_t* d_seg, const bcw_decode_params* p, const bcw_record_table* d_table,
-                  const bcw_decode_result* d_result, uint64_t src_fid, uint8_t* d_keep, bcw_index_result* d_out,
-                  bool pending) {
-  if (!x || !p || !d_table || !d_result || !d_keep || p->mode != BCW_MODE_RECORD) return BCW_E_INVAL;
-  bcw_ctx* c = x->ctx;
-  if (!c->s.frags || !d_table->foff || !d_table->key_len || !d_table->first_frag || !d_table->emit_frag ||
-      !d_table->hdr_size)
-    return BCW_E_INVAL;
-  DeviceGuard dg(c->device);
-  if (!dg.ok) return BCW_E_HIP;
-  const uint64_t rows = d_table->capacity;
-  hipStream_t st = c->cur;
-  (void)hipMemsetAsync(x->cnt + C_NIN, 0, 3 * sizeof(uint64_t), st);
-  uint64_t* rule_cnt = x->d_rule_cnt;
-  if (pending && x->rules.mask) {
-    rule_cnt += 3;
-    (void)hipMemsetAsync(rule_cnt, 0, 3 * sizeof(uint64_t), st);
-  }
-  const Src s = table_src(c, d_seg, p, d_table, SRC_RECORD);
-  const int rc = ix_launch_filter(x, s, rows, d_result, c->frag_gen, src_fid, d_keep, x->cnt, rule_cnt, st);
-  if (rc != BCW_OK) return rc;
-  if (d_out) k_ix_result<<<1, 1, 0, st>>>(x->cnt, d_out);
-  return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
-}
-}  // namespace
-
 namespace bcw {
+// bcw_compact_filter_async, with the rows the rules drop counted apart, for ix_rule_commit
 int ix_filter_pending(bcw_index* x, const uint8_t* d_seg, const bcw_decode_params* p, const bcw_record_table* d_table,
                       const bcw_decode_result* d_result, uint64_t src_fid, uint8_t* d_keep, bcw_index_result* d_out) {
-  return ix_filter_own(x, d_seg, p, d_table, d_result, src_fid, d_keep, d_out, true);
+  if (!x) return BCW_E_INVAL;
+  const bool apart = x->rules.mask != 0;  // rule counters [3, 6): the compaction in progress
+  return ix_filter(x, x->ctx, d_seg, p, d_table, d_result, src_fid, d_keep, x->cnt, x->d_rule_cnt + (apart ? 3 : 0),
+                   apart, d_out);
 }
 }  // namespace bcw
 
@@ -1591,8 +1658,7 @@ int bcw_index_reserve(bcw_index* x, uint64_t keys, uint64_t arena_bytes) {
   uint64_t c[C_NUM];
   int rc = ix_sync_counters(x, c);
   if (rc != BCW_OK) return rc;
-  x->slots_ub = c[C_SLOTS];
-  x->arena_ub = c[C_ARENA];
+  ix_refresh_bounds(x, c);
   return ix_grow(x, std::max(keys, x->slots_ub), std::max(arena_bytes, x->arena_ub));
 }
 
@@ -1656,23 +1722,20 @@ int bcw_index_apply_stat(bcw_index* x, uint64_t n, const uint8_t* h_keys, const 
   const bool stat = h_found || h_free_fid || h_free_bytes;
   if (stat && !(h_found && h_free_fid && h_free_bytes)) return BCW_E_INVAL;
   if (n == 0) return BCW_OK;
-  const uint64_t kb = h_key_off[n] - h_key_off[0];
-  if (kb && !h_keys) return BCW_E_INVAL;
+  int rc = flat_keys_ok(n, h_keys, h_key_off);
+  if (rc != BCW_OK) return rc;
   for (uint64_t i = 0; i < n; ++i)
-    if (h_key_off[i + 1] < h_key_off[i] || h_ops[i] > BCW_IDX_SOFT_DELETE) return BCW_E_INVAL;
+    if (h_ops[i] > BCW_IDX_SOFT_DELETE) return BCW_E_INVAL;
   DeviceGuard dg(x->ctx->device);
   if (!dg.ok) return BCW_E_HIP;
-  const uint64_t arena_b = 16 * n + kb + 15 * n;
-  int rc = ix_room(x, n, arena_b);
+  const uint64_t arena_b = 16 * n + (h_key_off[n] - h_key_off[0]) + 15 * n;
+  rc = ix_room(x, n, arena_b);
   if (rc != BCW_OK) return rc;
   // staging: keys | key offsets (rebased) | fid | off | size | WriteStat (fid, size) | ops | found
-  const uint64_t kbp = (kb + 15) & ~15ull;
-  rc = ix_stage(x, kbp + 8 * (n + 1) + 40 * n + 2 * n + 64);
+  FlatStage f;
+  rc = stage_flat_keys(x, n, h_keys, h_key_off, 40 * n + 2 * n, &f);
   if (rc != BCW_OK) return rc;
-  uint8_t* m = (uint8_t*)x->stage;
-  uint8_t* d_keys = m;
-  uint64_t* d_koff = (uint64_t*)(m + kbp);
-  uint64_t* d_fid = d_koff + (n + 1);
+  uint64_t* d_fid = (uint64_t*)f.rest;
   uint64_t* d_off = d_fid + n;
   uint64_t* d_size = d_off + n;
   uint64_t* d_ofid = d_size + n;
@@ -1680,22 +1743,13 @@ int bcw_index_apply_stat(bcw_index* x, uint64_t n, const uint8_t* h_keys, const 
   uint8_t* d_ops = (uint8_t*)(d_osize + n);
   uint8_t* d_found = d_ops + n;
   hipStream_t st = x->ctx->cur;
-  std::vector<uint64_t> koff(n + 1);
-  for (uint64_t i = 0; i <= n; ++i) koff[i] = h_key_off[i] - h_key_off[0];
-  bool ok = (kb == 0 || hipMemcpyAsync(d_keys, h_keys + h_key_off[0], kb, hipMemcpyHostToDevice, st) == hipSuccess) &&
-            hipMemcpyAsync(d_koff, koff.data(), 8 * (n + 1), hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(d_fid, h_fid, 8 * n, hipMemcpyHostToDevice, st) == hipSuccess &&
+  bool ok = hipMemcpyAsync(d_fid, h_fid, 8 * n, hipMemcpyHostToDevice, st) == hipSuccess &&
             hipMemcpyAsync(d_off, h_off, 8 * n, hipMemcpyHostToDevice, st) == hipSuccess &&
             hipMemcpyAsync(d_size, h_size, 8 * n, hipMemcpyHostToDevice, st) == hipSuccess &&
             hipMemcpyAsync(d_ops, h_ops, n, hipMemcpyHostToDevice, st) == hipSuccess;
   if (!ok) return BCW_E_HIP;
-  Src s{};
-  s.kind = SRC_FLAT;
-  s.keys = d_keys;
-  s.koff = d_koff;
-  s.keys_len = kb;
   OpVals v{d_ops, d_fid, d_off, d_size, 0, 0};
-  ix_batch(x, s, n, nullptr, 0, v, stat ? d_found : nullptr, d_ofid, d_osize);
+  ix_batch(x, f.src, n, nullptr, 0, v, stat ? d_found : nullptr, d_ofid, d_osize);
   if (stat)
     ok = hipMemcpyAsync(h_found, d_found, n, hipMemcpyDeviceToHost, st) == hipSuccess &&
          hipMemcpyAsync(h_free_fid, d_ofid, 8 * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
@@ -1751,36 +1805,22 @@ int bcw_index_get(bcw_index* x, uint64_t n, const uint8_t* h_keys, const uint64_
                   uint64_t* h_off, uint64_t* h_size, uint8_t* h_status) {
   if (!x || (n && (!h_key_off || !h_fid || !h_off || !h_size || !h_status))) return BCW_E_INVAL;
   if (n == 0) return BCW_OK;
-  const uint64_t kb = h_key_off[n] - h_key_off[0];
-  if (kb && !h_keys) return BCW_E_INVAL;
-  for (uint64_t i = 0; i < n; ++i)
-    if (h_key_off[i + 1] < h_key_off[i]) return BCW_E_INVAL;
+  int rc = flat_keys_ok(n, h_keys, h_key_off);
+  if (rc != BCW_OK) return rc;
   DeviceGuard dg(x->ctx->device);
   if (!dg.ok) return BCW_E_HIP;
-  const uint64_t kbp = (kb + 15) & ~15ull;
-  int rc = ix_stage(x, kbp + 8 * (n + 1) + 24 * n + n + 64);
+  // staging: keys | key offsets (rebased) | fid | off | size | status
+  FlatStage f;
+  rc = stage_flat_keys(x, n, h_keys, h_key_off, 24 * n + n, &f);
   if (rc != BCW_OK) return rc;
-  uint8_t* m = (uint8_t*)x->stage;
-  uint8_t* d_keys = m;
-  uint64_t* d_koff = (uint64_t*)(m + kbp);
-  uint64_t* d_fid = d_koff + (n + 1);
+  uint64_t* d_fid = (uint64_t*)f.rest;
   uint64_t* d_off = d_fid + n;
   uint64_t* d_size = d_off + n;
   uint8_t* d_st = (uint8_t*)(d_size + n);
   hipStream_t st = x->ctx->cur;
-  std::vector<uint64_t> koff(n + 1);
-  for (uint64_t i = 0; i <= n; ++i) koff[i] = h_key_off[i] - h_key_off[0];
-  bool ok = (kb == 0 || hipMemcpyAsync(d_keys, h_keys + h_key_off[0], kb, hipMemcpyHostToDevice, st) == hipSuccess) &&
-            hipMemcpyAsync(d_koff, koff.data(), 8 * (n + 1), hipMemcpyHostToDevice, st) == hipSuccess;
-  if (!ok) return BCW_E_HIP;
-  Src s{};
-  s.kind = SRC_FLAT;
-  s.keys = d_keys;
-  s.koff = d_koff;
-  s.keys_len = kb;
-  k_ix_get<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(s, n, x->slots, x->cap - 1, x->arena, d_fid, d_off, d_size,
-                                                         d_st);
-  ok = hipGetLastError() == hipSuccess &&
+  k_ix_get<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(f.src, n, x->slots, x->cap - 1, x->arena, d_fid, d_off,
+                                                         d_size, d_st);
+  const bool ok = hipGetLastError() == hipSuccess &&
        hipMemcpyAsync(h_fid, d_fid, 8 * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
        hipMemcpyAsync(h_off, d_off, 8 * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
        hipMemcpyAsync(h_size, d_size, 8 * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
@@ -1795,9 +1835,7 @@ int bcw_index_put_decoded_async(bcw_index* x, const uint8_t* d_seg, const bcw_de
   if (!x || !p || !d_table || !d_result) return BCW_E_INVAL;
   if (p->mode != BCW_MODE_RECORD && p->mode != BCW_MODE_HINT) return BCW_E_INVAL;
   bcw_ctx* c = x->ctx;
-  if (!c->s.frags || !d_table->foff || !d_table->size || !d_table->key_len || !d_table->first_frag ||
-      !d_table->emit_frag || !d_table->hdr_size)
-    return BCW_E_INVAL;
+  if (!table_ok(c, d_table, true)) return BCW_E_INVAL;
   if (p->mode == BCW_MODE_HINT && (!d_table->aux0 || !d_table->aux1 || !d_table->expire)) return BCW_E_INVAL;
   DeviceGuard dg(c->device);
   if (!dg.ok) return BCW_E_HIP;
@@ -1815,8 +1853,7 @@ int bcw_index_put_decoded_async(bcw_index* x, const uint8_t* d_seg, const bcw_de
     int rc0 = ix_sync_counters(x, cc);
     if (rc0 != BCW_OK) return rc0;
     if (cc[C_OVERFLOW]) return BCW_E_CAPACITY;
-    x->arena_ub = cc[C_ARENA];
-    x->slots_ub = cc[C_SLOTS];
+    ix_refresh_bounds(x, cc);
     arena_b = cc[C_NEED];
   }
   int rc = ix_room(x, rows, arena_b);
@@ -1830,7 +1867,8 @@ int bcw_index_put_decoded_async(bcw_index* x, const uint8_t* d_seg, const bcw_de
 int bcw_compact_filter_async(bcw_index* x, const uint8_t* d_seg, const bcw_decode_params* p,
                              const bcw_record_table* d_table, const bcw_decode_result* d_result, uint64_t src_fid,
                              uint8_t* d_keep, bcw_index_result* d_out) {
-  return ix_filter_own(x, d_seg, p, d_table, d_result, src_fid, d_keep, d_out, false);
+  if (!x) return BCW_E_INVAL;
+  return ix_filter(x, x->ctx, d_seg, p, d_table, d_result, src_fid, d_keep, x->cnt, x->d_rule_cnt, false, d_out);
 }
 
 int bcw_index_set_compact_rules(bcw_index* x, const bcw_compact_rules* r) {
@@ -1932,42 +1970,16 @@ int bcw_index_fid_usage_async(bcw_index* x, bcw_fid_usage* d_rows, uint32_t cap,
   uint64_t* scratch = nullptr;
   const int rc = usage_begin(c, st, &scratch);
   if (rc != BCW_OK) return rc;
-  if (x->slots && x->cap) {  // the buffers as they are now: a batch queued before this call has already grown them
-    const uint64_t wgs = (x->cap + kUsageSlots - 1) / kUsageSlots;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(wgs, (uint64_t)c->num_cus * 8);
-    hipEvent_t ev = nullptr;
-    c->prof.begin(K_USAGE_INDEX, st, ev);
+  const int rp = ix_usage_pass(x, K_USAGE_INDEX, st, [&](uint32_t grid) {
     k_ix_usage<<<grid, usage::kThreads, 0, st>>>(x->slots, x->cap, scratch);
-    c->prof.end(K_USAGE_INDEX, st, ev);
-    if (hipGetLastError() != hipSuccess) return BCW_E_HIP;
-  }
-  return usage_finish(c, st, d_rows, cap, d_res, 1);
+  });
+  return rp != BCW_OK ? rp : usage_finish(c, st, d_rows, cap, d_res, 1);
 }
 
 int bcw_index_fid_usage(bcw_index* x, bcw_fid_usage* h_rows, uint32_t cap, bcw_usage_result* h_res) {
-  if (!x || !h_res || (cap && !h_rows)) return BCW_E_INVAL;
-  bcw_ctx* c = x->ctx;
-  DeviceGuard dg(c->device);
-  if (!dg.ok) return BCW_E_HIP;
-  void* mem = nullptr;
-  if (hipMalloc(&mem, sizeof(bcw_usage_result) + (uint64_t)cap * sizeof(bcw_fid_usage)) != hipSuccess)
-    return BCW_E_NOMEM;
-  bcw_usage_result* d_res = static_cast<bcw_usage_result*>(mem);
-  bcw_fid_usage* d_rows = cap ? reinterpret_cast<bcw_fid_usage*>(d_res + 1) : nullptr;
-  int rc = bcw_index_fid_usage_async(x, d_rows, cap, d_res);
-  if (rc == BCW_OK &&
-      (hipMemcpyAsync(h_res, d_res, sizeof *h_res, hipMemcpyDeviceToHost, c->cur) != hipSuccess ||
-       hipStreamSynchronize(c->cur) != hipSuccess))
-    rc = BCW_E_HIP;
-  if (rc == BCW_OK && (!h_res->fits || h_res->overflow)) rc = BCW_E_CAPACITY;
-  if (rc == BCW_OK && h_res->n_fids &&
-      (hipMemcpyAsync(h_rows, d_rows, h_res->n_fids * sizeof(bcw_fid_usage), hipMemcpyDeviceToHost, c->cur) !=
-           hipSuccess ||
-       hipStreamSynchronize(c->cur) != hipSuccess))
-    rc = BCW_E_HIP;
-  (void)hipStreamSynchronize(c->cur);
-  (void)hipFree(mem);
-  return rc;
+  return ix_usage_sync(x, h_rows, cap, h_res, true, [&](bcw_fid_usage* d_rows, bcw_usage_result* d_res) {
+    return bcw_index_fid_usage_async(x, d_rows, cap, d_res);
+  });
 }
 
 int bcw_index_drop_fids_async(bcw_index* x, int mode, const uint64_t* h_fids, uint32_t n_fids, bcw_fid_usage* d_rows,
@@ -2011,78 +2023,22 @@ int bcw_index_drop_fids_async(bcw_index* x, int mode, const uint64_t* h_fids, ui
   uint64_t* scratch = nullptr;
   rc = usage_begin(c, st, &scratch);
   if (rc != BCW_OK) return rc;
-  if (x->slots && x->cap) {  // the buffers as they are now, as bcw_index_fid_usage_async takes them
-    const uint64_t wgs = (x->cap + kUsageSlots - 1) / kUsageSlots;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(wgs, (uint64_t)c->num_cus * 8);
-    hipEvent_t ev = nullptr;
-    c->prof.begin(K_IX_DROP, st, ev);
+  rc = ix_usage_pass(x, K_IX_DROP, st, [&](uint32_t grid) {
     k_ix_drop<<<grid, usage::kThreads, (size_t)nf * sizeof(uint64_t), st>>>(x->slots, x->cap, x->drop_d, nf, mode,
                                                                            scratch, x->cnt);
-    c->prof.end(K_IX_DROP, st, ev);
-    if (hipGetLastError() != hipSuccess) return BCW_E_HIP;
-  }
-  return usage_finish(c, st, d_rows, cap, d_res, 1);
+  });
+  return rc != BCW_OK ? rc : usage_finish(c, st, d_rows, cap, d_res, 1);
 }
 
 int bcw_index_drop_fids(bcw_index* x, int mode, const uint64_t* h_fids, uint32_t n_fids, bcw_fid_usage* h_rows,
                         uint32_t cap, bcw_usage_result* h_res) {
-  if (!x || !h_res || (cap && !h_rows)) return BCW_E_INVAL;
-  bcw_ctx* c = x->ctx;
-  DeviceGuard dg(c->device);
-  if (!dg.ok) return BCW_E_HIP;
-  void* mem = nullptr;
-  if (hipMalloc(&mem, sizeof(bcw_usage_result) + (uint64_t)cap * sizeof(bcw_fid_usage)) != hipSuccess)
-    return BCW_E_NOMEM;
-  bcw_usage_result* d_res = static_cast<bcw_usage_result*>(mem);
-  bcw_fid_usage* d_rows = cap ? reinterpret_cast<bcw_fid_usage*>(d_res + 1) : nullptr;
-  int rc = bcw_index_drop_fids_async(x, mode, h_fids, n_fids, d_rows, cap, d_res);
-  if (rc == BCW_OK &&
-      (hipMemcpyAsync(h_res, d_res, sizeof *h_res, hipMemcpyDeviceToHost, c->cur) != hipSuccess ||
-       hipStreamSynchronize(c->cur) != hipSuccess))
-    rc = BCW_E_HIP;
   // fits == 0 and overflow are the caller's to read: the drop has happened either way
-  if (rc == BCW_OK && h_res->fits && !h_res->overflow && h_res->n_fids &&
-      (hipMemcpyAsync(h_rows, d_rows, h_res->n_fids * sizeof(bcw_fid_usage), hipMemcpyDeviceToHost, c->cur) !=
-           hipSuccess ||
-       hipStreamSynchronize(c->cur) != hipSuccess))
-    rc = BCW_E_HIP;
-  (void)hipStreamSynchronize(c->cur);
-  (void)hipFree(mem);
-  return rc;
+  return ix_usage_sync(x, h_rows, cap, h_res, false, [&](bcw_fid_usage* d_rows, bcw_usage_result* d_res) {
+    return bcw_index_drop_fids_async(x, mode, h_fids, n_fids, d_rows, cap, d_res);
+  });
 }
 
-uint64_t bcw_murmur3_sum64(const uint8_t* p, uint64_t n) {
-  // host restatement of the device hash (spaolacci/murmur3 New64().Sum64(), index.go:15-19)
-  const uint64_t c1 = 0x87c37b91114253d5ull, c2 = 0x4cf5ad432745937full;
-  auto rl = [](uint64_t v, int r) { return (v << r) | (v >> (64 - r)); };
-  auto fm = [](uint64_t k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return k;
-  };
-  uint64_t h1 = 0, h2 = 0;
-  const uint64_t nb = n / 16;
-  for (uint64_t i = 0; i < nb; ++i) {
-    uint64_t k1, k2;
-    memcpy(&k1, p + 16 * i, 8);
-    memcpy(&k2, p + 16 * i + 8, 8);
-    k1 *= c1; k1 = rl(k1, 31); k1 *= c2; h1 ^= k1;
-    h1 = rl(h1, 27); h1 += h2; h1 = h1 * 5 + 0x52dce729;
-    k2 *= c2; k2 = rl(k2, 33); k2 *= c1; h2 ^= k2;
-    h2 = rl(h2, 31); h2 += h1; h2 = h2 * 5 + 0x38495ab5;
-  }
-  uint64_t k1 = 0, k2 = 0;
-  const uint64_t t = n & 15;
-  for (uint64_t i = 0; i < t; ++i) {
-    const uint64_t b = p[16 * nb + i];
-    if (i < 8) k1 |= b << (8 * i); else k2 |= b << (8 * (i - 8));
-  }
-  if (t > 8) { k2 *= c2; k2 = rl(k2, 33); k2 *= c1; h2 ^= k2; }
-  if (t > 0) { k1 *= c1; k1 = rl(k1, 31); k1 *= c2; h1 ^= k1; }
-  h1 ^= n; h2 ^= n;
-  h1 += h2; h2 += h1;
-  h1 = fm(h1); h2 = fm(h2);
-  h1 += h2;
-  return h1;
-}
+// the hash of the index (bcw_murmur.h: the text the kernels compile), over a byte pointer
+uint64_t bcw_murmur3_sum64(const uint8_t* p, uint64_t n) { return murmur::sum64(p, n); }
 
 }  // extern "C"
