@@ -14,93 +14,10 @@
 
 #include "bcw.h"
 #include "bcw_frame.h"
-#include "bcw_internal.h"
+#include "bcw_crc_tables.h"
+#include "bcw_host.h"
 
 namespace bcw {
-
-// ---- CRC-32C constant tables (reflected polynomial 0x82F63B78, Go crc32.Castagnoli) ----
-static void byte_table(uint32_t* t0) {
-  for (uint32_t b = 0; b < 256; ++b) {
-    uint32_t c = b;
-    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
-    t0[b] = c;
-  }
-}
-
-static inline uint32_t zero_step(const uint32_t* t0, uint32_t s) { return (s >> 8) ^ t0[s & 0xffu]; }
-
-// images of the 32 basis vectors under "advance over n zero bytes"
-static void shift_basis(const uint32_t* t0, uint64_t n, uint32_t* img) {
-  for (int i = 0; i < 32; ++i) {
-    uint32_t v = 1u << i;
-    for (uint64_t k = 0; k < n; ++k) v = zero_step(t0, v);
-    img[i] = v;
-  }
-}
-static inline uint32_t apply_basis(const uint32_t* img, uint32_t x) {
-  uint32_t r = 0;
-  for (int i = 0; x; ++i, x >>= 1)
-    if (x & 1u) r ^= img[i];
-  return r;
-}
-
-// basis images of the inverse of a (bijective) GF(2)-linear map given by its basis images
-static void invert_basis(const uint32_t* img, uint32_t* inv) {
-  uint32_t out[32], in[32];
-  for (int i = 0; i < 32; ++i) { out[i] = img[i]; in[i] = 1u << i; }
-  for (int bit = 0; bit < 32; ++bit) {
-    int p = bit;
-    while (p < 32 && !((out[p] >> bit) & 1u)) ++p;  // x^8n mod P is invertible: a pivot always exists
-    std::swap(out[bit], out[p]);
-    std::swap(in[bit], in[p]);
-    for (int r = 0; r < 32; ++r)
-      if (r != bit && ((out[r] >> bit) & 1u)) { out[r] ^= out[bit]; in[r] ^= in[bit]; }
-  }
-  for (int bit = 0; bit < 32; ++bit) inv[bit] = in[bit];
-}
-
-static void nibble_image(const uint32_t* img, uint32_t* t) {
-  for (int i = 0; i < 8; ++i)
-    for (uint32_t n = 0; n < 16; ++n) t[i * 16 + n] = apply_basis(img, n << (4 * i));
-}
-
-// encode shift operators (nibble images, 128 words each; layout in bcw_internal.h): A_{8*16*n},
-// A_{8*256*n}, A_{8*4096*n} (k_write's lane chains), A_{8t}^-1 (t < 16), and A_{8*2^k} / A_{8*2^k}^-1 for
-// shifts by arbitrary distances (the CRC combine of re-encoded records)
-static void build_enc_ops(uint32_t* ops) {
-  uint32_t t0[256];
-  byte_table(t0);
-  uint32_t img[32], inv[32], sq[32];
-  for (int n = 0; n < 16; ++n) { shift_basis(t0, 16ull * n, img); nibble_image(img, ops + n * 128); }
-  for (int n = 0; n < 16; ++n) { shift_basis(t0, 256ull * n, img); nibble_image(img, ops + (16 + n) * 128); }
-  for (int n = 0; n < 8; ++n) { shift_basis(t0, 4096ull * n, img); nibble_image(img, ops + (32 + n) * 128); }
-  for (int t = 0; t < 16; ++t) {
-    shift_basis(t0, (uint64_t)t, img);
-    invert_basis(img, inv);
-    nibble_image(inv, ops + (kOpInv + t) * 128);
-  }
-  shift_basis(t0, 1, img);  // A_8, then repeated squaring
-  for (int k = 0; k < 32; ++k) {
-    nibble_image(img, ops + (kOpPow2 + k) * 128);
-    if (k < 15) {
-      invert_basis(img, inv);
-      nibble_image(inv, ops + (kOpPow2Inv + k) * 128);
-    }
-    for (int i = 0; i < 32; ++i) sq[i] = apply_basis(img, img[i]);
-    memcpy(img, sq, sizeof img);
-  }
-}
-
-// initc[L] = A_{8L}(0xFFFFFFFF): the contribution of the CRC init value after L data bytes
-void build_initc(uint32_t* initc) {
-  uint32_t t0[256];
-  byte_table(t0);
-  uint32_t v = 0xffffffffu;
-  for (uint32_t L = 0; L <= kBlock; ++L) {
-    initc[L] = v;
-    v = zero_step(t0, v);
-  }
-}
 
 // ---- host CRC-32C (SSE4.2) for the writer and bcw_crc32c_masked ----
 static uint32_t crc32c_hw(const uint8_t* p, size_t n) {
@@ -242,149 +159,33 @@ int bcw_ctx_create(int device, bcw_ctx** out) {
     c->num_cus = prop.multiProcessorCount;
   if (hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking) != hipSuccess) { delete c; return BCW_E_HIP; }
   c->cur = c->own;
-  std::vector<uint32_t> initc(kBlock + 1);
-  build_initc(initc.data());
-  std::vector<uint32_t> enc_ops(kEncOpsWords);
-  build_enc_ops(enc_ops.data());
-  std::vector<uint32_t> pow2(kPow2Ops * 128);
-  {
-    uint32_t t0[256], img[32], sq[32];
-    byte_table(t0);
-    shift_basis(t0, 1, img);  // A_8, then repeated squaring: A_{8*2^(k+1)} = A_{8*2^k} o A_{8*2^k}
-    for (int k = 0; k < kPow2Ops; ++k) {
-      nibble_image(img, pow2.data() + k * 128);
-      for (int i = 0; i < 32; ++i) sq[i] = apply_basis(img, img[i]);
-      memcpy(img, sq, sizeof img);
-    }
-  }
-  std::vector<uint32_t> image2(kS2Image);
-  {  // stream verify (bcw_internal.h kS2*): slice rows with the shifted tables, lane operators, split operators
-    uint32_t tk[4][256], t0[256], img[32], nib[128], step[32], m[32];
-    byte_table(t0);
-    memcpy(tk[0], t0, sizeof t0);
-    for (int k = 1; k < 4; ++k)
-      for (int e = 0; e < 256; ++e) tk[k][e] = (tk[k - 1][e] >> 8) ^ t0[tk[k - 1][e] & 0xffu];
-    uint32_t sh[32];
-    shift_basis(t0, kSChunk - kSPiece, sh);
-    for (int e = 0; e < 256; ++e)
-      for (int s = 0; s < 4; ++s)
-        for (int cp = 0; cp < 8; ++cp) {
-          image2[kS2SliceOff + e * 64 + s * 8 + cp] = tk[3 - s][e];
-          image2[kS2SliceOff + e * 64 + 32 + s * 8 + cp] = apply_basis(sh, tk[3 - s][e]);
-        }
-    shift_basis(t0, kSPiece, step);
-    for (int i = 0; i < 32; ++i) m[i] = 1u << i;  // identity for lane 63
-    for (int l = 63; l >= 0; --l) {
-      nibble_image(m, nib);
-      for (int k = 0; k < 128; ++k) image2[kS2LopOff + k * 64 + l] = nib[k];
-      for (int i = 0; i < 32; ++i) m[i] = apply_basis(step, m[i]);
-    }
-    for (int k = 0; k < kSPW; ++k) {  // split operators as byte tables: [k][t][e] = A(e << 8t)
-      shift_basis(t0, 4u * (kSPW - k) + (kSChunk - kSPiece), img);
-      for (int t = 0; t < 4; ++t)
-        for (uint32_t e = 0; e < 256; ++e)
-          image2[kS2KopOff + (k * 4 + t) * 256 + e] = apply_basis(img, e << (8 * t));
-    }
-    auto put_bytes = [&](int at, const uint8_t (&b)[16]) {
-      for (int w = 0; w < 4; ++w)
-        image2[at + w] = b[4 * w] | b[4 * w + 1] << 8 | b[4 * w + 2] << 16 | (uint32_t)b[4 * w + 3] << 24;
-    };
-    for (int n = 0; n < kS2GeN; ++n) {  // GE[n]: bytes q >= n
-      uint8_t b[16];
-      for (int q = 0; q < 16; ++q) b[q] = q >= n ? 0xff : 0x00;
-      put_bytes(kS2Ge + 4 * n, b);
-    }
-    for (int m = 0; m < kS2JselN; ++m) {  // JSEL[m]: perm selectors, J byte q - o at q in [o, o + 4) (o = m - 3), else 0
-      uint8_t b[16];
-      for (int q = 0; q < 16; ++q) {
-        const int p = q - (m - 3);
-        b[q] = (m < kS2JselN - 1 && p >= 0 && p < 4) ? (uint8_t)(4 + p) : 0x0c;
-      }
-      put_bytes(kS2Jsel + 4 * m, b);
-    }
-    for (int g = 0; g < kS2GapN; ++g) {  // GAP[g]: J at [o, o + 4) (o = g - 6), zeros at [o + 4, o + 7), else the byte
-      uint8_t b[16];
-      for (int q = 0; q < 16; ++q) {
-        const int p = q - (g - 6);
-        b[q] = g == kS2GapN - 1 ? (uint8_t)(q & 3) : (p >= 0 && p < 4) ? (uint8_t)(4 + p) : (p >= 4 && p < 7) ? 0x0c
-                                                                                            : (uint8_t)(q & 3);
-      }
-      put_bytes(kS2Gap + 4 * g, b);
-    }
-  }
-  bool ok = hipMalloc(&c->tabs.lds_image2, image2.size() * 4) == hipSuccess &&
-            hipMemcpy(c->tabs.lds_image2, image2.data(), image2.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-  ok = ok && hipMalloc(&c->tabs.initc, initc.size() * 4) == hipSuccess &&
-            hipMalloc(&c->tabs.enc_ops, enc_ops.size() * 4) == hipSuccess &&
-            hipMalloc(&c->tabs.pow2, pow2.size() * 4) == hipSuccess &&
-            hipMalloc(&c->d_eres, sizeof(bcw_encode_result)) == hipSuccess &&
-            hipMalloc(&c->d_result, sizeof(bcw_decode_result)) == hipSuccess &&
-            hipMalloc(&c->d_ires, sizeof(bcw_index_result)) == hipSuccess;
-  ok = ok && hipMemcpy(c->tabs.initc, initc.data(), initc.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(c->tabs.enc_ops, enc_ops.data(), enc_ops.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(c->tabs.pow2, pow2.data(), pow2.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+  const crc::Tables T = crc::build_tables();
+  auto upload = [](DevBuf<uint32_t>& d, const std::vector<uint32_t>& h) {
+    return d.alloc(h.size() * 4) && hipMemcpy(d.get(), h.data(), h.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+  };
+  const bool ok = upload(c->d_image2, T.lds_image2) && upload(c->d_initc, T.initc) && upload(c->d_enc_ops, T.enc_ops) &&
+                  upload(c->d_pow2, T.pow2) && c->d_eres.alloc(sizeof(bcw_encode_result)) &&
+                  c->d_result.alloc(sizeof(bcw_decode_result)) && c->d_ires.alloc(sizeof(bcw_index_result));
+  c->tabs = Tables{c->d_initc.get(), c->d_image2.get(), c->d_enc_ops.get(), c->d_pow2.get()};
   if (!ok) { bcw_ctx_destroy(c); return BCW_E_NOMEM; }
   *out = c;
   return BCW_OK;
 }
 
-static void free_scratch(Scratch& s) {
-  (void)hipFree(s.fbase);
-  (void)hipFree(s.rbase);
-  (void)hipFree(s.bsum);
-  (void)hipFree(s.lb);
-  (void)hipFree(s.lbe);
-  (void)hipFree(s.frags);
-  (void)hipFree(s.srec);
-  (void)hipFree(s.fok);
-  (void)hipFree(s.wstart);
-  (void)hipFree(s.xbal);
-  (void)hipFree(s.misc);
-  s = Scratch{};
-}
-
-static void free_enc_scratch(EncScratch& e) {
-  void* ptrs[] = {e.sz,    e.mflag, e.dsrc, e.da,      e.hda,       e.hsz,  e.dpos,
-                  e.hpos,  e.tiles, e.ev,   e.evb,     e.recdesc,   e.emisc, e.evt,
-                  e.hnl,   e.evw,   e.wl};
-  for (void* q : ptrs) (void)hipFree(q);
-  hipStream_t aux = e.aux;
-  hipEvent_t evs[3] = {e.ev_scan, e.ev_hscan, e.ev_desc};
-  e = EncScratch{};
-  e.aux = aux;  // the auxiliary stream and its events live as long as the context
-  e.ev_scan = evs[0];
-  e.ev_hscan = evs[1];
-  e.ev_desc = evs[2];
-}
-
 int bcw_ctx_destroy(bcw_ctx* c) {
   if (!c) return BCW_E_INVAL;
   DeviceGuard dg(c->device);
+  // the streams first: nothing is freed under work still queued. The buffers go with the context (DevBuf).
   if (c->cur) (void)hipStreamSynchronize(c->cur);
-  free_scratch(c->s);
-  free_enc_scratch(c->es);
-  put_scratch_free(c->ps);
-  if (c->es.aux) (void)hipStreamSynchronize(c->es.aux);
-  if (c->es.ev_scan) (void)hipEventDestroy(c->es.ev_scan);
-  if (c->es.ev_hscan) (void)hipEventDestroy(c->es.ev_hscan);
-  if (c->es.ev_desc) (void)hipEventDestroy(c->es.ev_desc);
-  if (c->es.aux) (void)hipStreamDestroy(c->es.aux);
-  (void)hipFree(c->tabs.enc_ops);
-  (void)hipFree(c->tabs.pow2);
-  (void)hipFree(c->d_keep);
-  (void)hipFree(c->d_eout);
-  (void)hipFree(c->d_eres);
-  (void)hipFree(c->tabs.initc);
-  (void)hipFree(c->tabs.lds_image2);
-  (void)hipFree(c->d_seg);
-  (void)hipFree(c->d_tab_mem);
-  (void)hipFree(c->d_result);
-  (void)hipFree(c->d_ires);
-  (void)hipFree(c->usage);
+  if (c->ea.aux) (void)hipStreamSynchronize(c->ea.aux);
+  for (hipEvent_t e : {c->ea.ev_scan, c->ea.ev_hscan, c->ea.ev_desc})
+    if (e) (void)hipEventDestroy(e);
+  if (c->ea.aux) (void)hipStreamDestroy(c->ea.aux);
   for (auto& m : c->prof.marks) { (void)hipEventDestroy(m.a); (void)hipEventDestroy(m.b); }
   for (auto e : c->prof.pool) (void)hipEventDestroy(e);
-  if (c->own) (void)hipStreamDestroy(c->own);
+  hipStream_t own = c->own;
   delete c;
+  if (own) (void)hipStreamDestroy(own);
   return BCW_OK;
 }
 
@@ -406,19 +207,16 @@ static int ensure_scratch(bcw_ctx* c, uint64_t nblocks, uint64_t frag_cap) {
   (void)hipStreamSynchronize(c->cur);
   const uint64_t nb = std::max(nblocks, s.nblocks_cap);
   const uint64_t fc = std::max(frag_cap, s.frag_cap);
-  free_scratch(s);
+  s = Scratch{};  // frees every array
   // look-back words: one per 64-block k_chase workgroup. The stream records have 4 entries of slack: k_crc's stream
   // loads the record after a wave's current fragment unconditionally (bcw_decode.hip, stream_verify)
   const uint64_t nwg = std::max<uint64_t>(nb / 64 + 2, (uint64_t)c->num_cus + 2);
-  bool ok = hipMalloc(&s.fbase, (nb + 1) * 4) == hipSuccess && hipMalloc(&s.rbase, (nb + 1) * 4) == hipSuccess &&
-            hipMalloc(&s.bsum, (nb + 1) * sizeof(uint2)) == hipSuccess && hipMalloc(&s.lb, nwg * 8) == hipSuccess &&
-            hipMalloc(&s.lbe, nwg * 8) == hipSuccess && hipMalloc(&s.frags, fc * sizeof(Frag)) == hipSuccess &&
-            hipMalloc(&s.srec, (fc + 4) * sizeof(uint4)) == hipSuccess &&
-            hipMalloc(&s.fok, fc) == hipSuccess &&
-            hipMalloc(&s.wstart, ((size_t)c->num_cus * kCrcWaves + 1) * 4) == hipSuccess &&
-            hipMalloc(&s.xbal, sizeof(XBal)) == hipSuccess &&
-            hipMalloc(&s.misc, 16 * sizeof(uint64_t)) == hipSuccess;
-  if (!ok) { free_scratch(s); return BCW_E_NOMEM; }
+  const bool ok = s.fbase.alloc((nb + 1) * 4) && s.rbase.alloc((nb + 1) * 4) && s.bsum.alloc((nb + 1) * sizeof(uint2)) &&
+                  s.lb.alloc(nwg * 8) && s.lbe.alloc(nwg * 8) && s.frags.alloc(fc * sizeof(Frag)) &&
+                  s.srec.alloc((fc + 4) * sizeof(uint4)) && s.fok.alloc(fc) &&
+                  s.wstart.alloc(((size_t)c->num_cus * kCrcWaves + 1) * 4) && s.xbal.alloc(sizeof(XBal)) &&
+                  s.misc.alloc(16 * sizeof(uint64_t));
+  if (!ok) { s = Scratch{}; return BCW_E_NOMEM; }
   s.nblocks_cap = nb;
   s.frag_cap = fc;
   s.nlb = nwg;
@@ -431,12 +229,14 @@ static int ensure_scratch(bcw_ctx* c, uint64_t nblocks, uint64_t frag_cap) {
   // misc[0] (first bad record) and misc[14] (first CRC failure) start at UINT64_MAX too
   XBal xb{};  // equal weights to begin with; k_crc's finalize adapts them decode by decode
   for (uint32_t y = 0; y < 8; ++y) xb.w[y] = 65536u;
-  if (hipMemcpyHtoDAsync(s.xbal, &xb, sizeof xb, c->cur) != hipSuccess || hipStreamSynchronize(c->cur) != hipSuccess ||
-      hipMemsetAsync(s.lb, 0, nwg * 8, c->cur) != hipSuccess || hipMemsetAsync(s.lbe, 0, nwg * 8, c->cur) != hipSuccess ||
-      hipMemsetAsync(s.misc, 0, 16 * sizeof(uint64_t), c->cur) != hipSuccess ||
-      hipMemsetAsync(s.misc + 14, 0xff, 2 * sizeof(uint64_t), c->cur) != hipSuccess ||
-      hipMemsetAsync(s.misc, 0xff, sizeof(uint64_t), c->cur) != hipSuccess) {
-    free_scratch(s);
+  uint64_t* misc = s.misc.get();
+  if (hipMemcpyHtoDAsync(s.xbal.get(), &xb, sizeof xb, c->cur) != hipSuccess ||
+      hipStreamSynchronize(c->cur) != hipSuccess || hipMemsetAsync(s.lb.get(), 0, nwg * 8, c->cur) != hipSuccess ||
+      hipMemsetAsync(s.lbe.get(), 0, nwg * 8, c->cur) != hipSuccess ||
+      hipMemsetAsync(misc, 0, 16 * sizeof(uint64_t), c->cur) != hipSuccess ||
+      hipMemsetAsync(misc + 14, 0xff, 2 * sizeof(uint64_t), c->cur) != hipSuccess ||
+      hipMemsetAsync(misc, 0xff, sizeof(uint64_t), c->cur) != hipSuccess) {
+    s = Scratch{};
     return BCW_E_HIP;
   }
   return BCW_OK;
@@ -446,9 +246,7 @@ int bcw_decode_segment_async(bcw_ctx* c, const uint8_t* d_seg, const bcw_decode_
                              const bcw_record_table* t, bcw_decode_result* d_result) {
   if (!c || !p || !t || !d_result) return BCW_E_INVAL;
   if (p->mode != BCW_MODE_RECORD && p->mode != BCW_MODE_HINT) return BCW_E_INVAL;
-  if (!t->foff || !t->size || !t->expire || !t->key_len || !t->val_len || !t->meta_len || !t->first_frag ||
-      !t->emit_frag || !t->hdr_size || !t->flags || !t->etag_off || !t->status)
-    return BCW_E_INVAL;
+  if (!table_has(*t, kColAux)) return BCW_E_INVAL;
   if (p->mode == BCW_MODE_HINT && (!t->aux0 || !t->aux1)) return BCW_E_INVAL;
   if (p->seg_len > BCW_MAX_SEGMENT) return BCW_E_INVAL;  // k_crc's item arithmetic is 32-bit (< 2^24 blocks)
   DeviceGuard dg(c->device);
@@ -582,22 +380,15 @@ int bcw_decode_fragments(bcw_ctx* c, const bcw_frag_table* h, uint64_t* n_total)
   DeviceGuard dg(c->device);
   if (!dg.ok) return BCW_E_HIP;
   uint64_t misc[16];
-  HIPCHK(hipMemcpyAsync(misc, c->s.misc, sizeof misc, hipMemcpyDeviceToHost, c->cur));
+  HIPCHK(hipMemcpyAsync(misc, c->s.misc.get(), sizeof misc, hipMemcpyDeviceToHost, c->cur));
   HIPCHK(hipStreamSynchronize(c->cur));
   const uint64_t total = std::min(misc[4], c->s.frag_cap);
   if (n_total) *n_total = total;
   const uint64_t n = std::min(total, h->capacity);
   if (n == 0) return BCW_OK;
-  void* mem = nullptr;
-  if (hipMalloc(&mem, n * 19) != hipSuccess) return BCW_E_NOMEM;
-  uint8_t* m = (uint8_t*)mem;
+  DevBuf<> mem;
   bcw_frag_table d;
-  d.capacity = n;
-  d.data_off = (uint64_t*)m; m += n * 8;
-  d.len = (uint32_t*)m; m += n * 4;
-  d.stored_crc = (uint32_t*)m; m += n * 4;
-  d.type = m; m += n;
-  d.crc_ok = m;
+  if (const int rc = carve_alloc(mem, [&](Carver& cv) { d = carve_frags(cv, n); })) return rc;
   bool ok = launch_export_frags(c->s, d, c->last_start_off, c->cur, n, c->tabs.initc) == hipSuccess;
   auto cp = [&](void* dst, const void* src, size_t esz) {
     return !dst || hipMemcpyAsync(dst, src, n * esz, hipMemcpyDeviceToHost, c->cur) == hipSuccess;
@@ -605,38 +396,43 @@ int bcw_decode_fragments(bcw_ctx* c, const bcw_frag_table* h, uint64_t* n_total)
   ok = ok && cp(h->data_off, d.data_off, 8) && cp(h->len, d.len, 4) && cp(h->stored_crc, d.stored_crc, 4) &&
        cp(h->type, d.type, 1) && cp(h->crc_ok, d.crc_ok, 1);
   ok = ok && hipStreamSynchronize(c->cur) == hipSuccess;
-  (void)hipFree(mem);
   return ok ? BCW_OK : BCW_E_HIP;
 }
 
-static int ensure_dev_table(bcw_ctx* c, uint64_t cap, bool hint) {
-  if (cap <= c->d_tab_cap && c->d_tab_mem) return BCW_OK;
-  (void)hipStreamSynchronize(c->cur);
-  (void)hipFree(c->d_tab_mem);
-  c->d_tab_mem = nullptr;
+// the context's device table (grow-only), all columns, at least `cap` rows
+static int ensure_dev_table(bcw_ctx* c, uint64_t cap) {
+  if (cap <= c->d_tab.capacity && c->d_tab_mem) return BCW_OK;
   const uint64_t n = std::max<uint64_t>(cap, 1);
-  const size_t bytes = n * (8 * 5 + 4 * 5 + 4);
-  if (hipMalloc(&c->d_tab_mem, bytes) != hipSuccess) { c->d_tab_cap = 0; return BCW_E_NOMEM; }
-  uint8_t* m = (uint8_t*)c->d_tab_mem;
-  bcw_record_table& t = c->d_tab;
-  t.capacity = n;
-  t.foff = (uint64_t*)m; m += n * 8;
-  t.size = (uint64_t*)m; m += n * 8;
-  t.expire = (uint64_t*)m; m += n * 8;
-  t.aux0 = (uint64_t*)m; m += n * 8;
-  t.aux1 = (uint64_t*)m; m += n * 8;
-  t.key_len = (uint32_t*)m; m += n * 4;
-  t.val_len = (uint32_t*)m; m += n * 4;
-  t.meta_len = (uint32_t*)m; m += n * 4;
-  t.first_frag = (uint32_t*)m; m += n * 4;
-  t.emit_frag = (uint32_t*)m; m += n * 4;
-  t.hdr_size = m; m += n;
-  t.flags = m; m += n;
-  t.etag_off = m; m += n;
-  t.status = m;
-  c->d_tab_cap = n;
-  (void)hint;
+  c->d_tab = bcw_record_table{};
+  Carver measure;
+  carve_table(measure, n, true);
+  if (!c->d_tab_mem.reserve(measure.total(), c->cur)) return BCW_E_NOMEM;
+  Carver cv(c->d_tab_mem.get(), measure.total());
+  c->d_tab = carve_table(cv, n, true);
   return BCW_OK;
+}
+
+// Upload the segment and decode it into the context's device table of `rows` rows, the fragment scratch retried until
+// it fits; with `grow` the table is enlarged and the decode repeated until it holds every record. *res: the last result.
+static int decode_staged(bcw_ctx* c, const uint8_t* h_seg, const bcw_decode_params& p, bcw_decode_result* res,
+                         uint64_t rows, bool grow) {
+  if (!c->d_seg.reserve(p.seg_len, c->cur)) return BCW_E_NOMEM;
+  if (p.seg_len) HIPCHK(hipMemcpyAsync(c->d_seg.get(), h_seg, p.seg_len, hipMemcpyHostToDevice, c->cur));
+  for (;;) {
+    int rc = ensure_dev_table(c, rows);
+    if (rc != BCW_OK) return rc;
+    for (int attempt = 0; attempt < 3; ++attempt) {
+      rc = bcw_decode_segment_async(c, c->d_seg.get(), &p, &c->d_tab, c->d_result.get());
+      if (rc != BCW_OK) return rc;
+      HIPCHK(hipMemcpyAsync(res, c->d_result.get(), sizeof *res, hipMemcpyDeviceToHost, c->cur));
+      HIPCHK(hipStreamSynchronize(c->cur));
+      if (!res->retry_frag_capacity) break;
+      if (bcw_ctx_reserve_fragments(c, res->retry_frag_capacity + 64) != BCW_OK) return BCW_E_CAPACITY;
+    }
+    if (res->retry_frag_capacity) return BCW_E_NOMEM;
+    if (!grow || res->n_records <= c->d_tab.capacity) return BCW_OK;
+    rows = res->n_records + 16;
+  }
 }
 
 int bcw_decode_segment(bcw_ctx* c, const uint8_t* h_seg, const bcw_decode_params* p,
@@ -645,73 +441,14 @@ int bcw_decode_segment(bcw_ctx* c, const uint8_t* h_seg, const bcw_decode_params
   if (p->seg_len && !h_seg) return BCW_E_INVAL;
   DeviceGuard dg(c->device);
   if (!dg.ok) return BCW_E_HIP;
-  if (p->seg_len > c->d_seg_cap) {
-    (void)hipStreamSynchronize(c->cur);
-    (void)hipFree(c->d_seg);
-    c->d_seg = nullptr;
-    c->d_seg_cap = 0;
-    if (hipMalloc(&c->d_seg, p->seg_len) != hipSuccess) return BCW_E_NOMEM;
-    c->d_seg_cap = p->seg_len;
-  }
-  if (p->seg_len) HIPCHK(hipMemcpyAsync(c->d_seg, h_seg, p->seg_len, hipMemcpyHostToDevice, c->cur));
-  int rc = ensure_dev_table(c, h->capacity, p->mode == BCW_MODE_HINT);
+  const int rc = decode_staged(c, h_seg, *p, h_result, h->capacity, false);
   if (rc != BCW_OK) return rc;
-  for (int attempt = 0; attempt < 3; ++attempt) {
-    rc = bcw_decode_segment_async(c, c->d_seg, p, &c->d_tab, c->d_result);
-    if (rc != BCW_OK) return rc;
-    HIPCHK(hipMemcpyAsync(h_result, c->d_result, sizeof *h_result, hipMemcpyDeviceToHost, c->cur));
-    HIPCHK(hipStreamSynchronize(c->cur));
-    if (!h_result->retry_frag_capacity) break;
-    if (bcw_ctx_reserve_fragments(c, h_result->retry_frag_capacity + 64) != BCW_OK) return BCW_E_CAPACITY;
-  }
-  if (h_result->retry_frag_capacity) return BCW_E_NOMEM;
-  const uint64_t n = std::min(h_result->n_records, h->capacity);
-  const bcw_record_table& d = c->d_tab;
-  auto cp = [&](void* dst, const void* src, size_t esz) -> bool {
-    if (!dst || n == 0) return true;
-    return hipMemcpyAsync(dst, src, n * esz, hipMemcpyDeviceToHost, c->cur) == hipSuccess;
-  };
-  bool ok = cp(h->foff, d.foff, 8) && cp(h->size, d.size, 8) && cp(h->expire, d.expire, 8) &&
-            cp(h->aux0, d.aux0, 8) && cp(h->aux1, d.aux1, 8) && cp(h->key_len, d.key_len, 4) &&
-            cp(h->val_len, d.val_len, 4) && cp(h->meta_len, d.meta_len, 4) && cp(h->first_frag, d.first_frag, 4) &&
-            cp(h->emit_frag, d.emit_frag, 4) && cp(h->hdr_size, d.hdr_size, 1) && cp(h->flags, d.flags, 1) &&
-            cp(h->etag_off, d.etag_off, 1) && cp(h->status, d.status, 1);
-  if (!ok) return BCW_E_HIP;
+  if (!table_copy_down(*h, c->d_tab, std::min(h_result->n_records, h->capacity), c->cur)) return BCW_E_HIP;
   HIPCHK(hipStreamSynchronize(c->cur));
   return h_result->n_records > h->capacity ? BCW_E_CAPACITY : BCW_OK;
 }
 
-
 // ---- encode (bcw_encode.hip) ----
-static int ensure_enc_scratch(bcw_ctx* c, uint64_t rows) {
-  EncScratch& e = c->es;
-  if (rows <= e.rows_cap && e.emisc) return BCW_OK;
-  (void)hipStreamSynchronize(c->cur);
-  const uint64_t r = std::max(std::max(rows, e.rows_cap), (uint64_t)1);
-  free_enc_scratch(e);
-  const uint64_t ntiles = r / enc_tile_items() + 2;
-  const uint64_t nwin = r / enc_ev_win() + 2;
-  bool ok = hipMalloc(&e.sz, r * 4) == hipSuccess && hipMalloc(&e.mflag, r) == hipSuccess &&
-            hipMalloc(&e.dsrc, r * 4) == hipSuccess && hipMalloc(&e.da, (r + 1) * 8) == hipSuccess &&
-            hipMalloc(&e.hda, (r + 1) * 8) == hipSuccess && hipMalloc(&e.hsz, r * 4) == hipSuccess &&
-            hipMalloc(&e.dpos, r * 8) == hipSuccess && hipMalloc(&e.hpos, r * 8) == hipSuccess &&
-            hipMalloc(&e.tiles, ntiles * enc_sizeof_tile()) == hipSuccess &&
-            hipMalloc(&e.ev, (r + 2) * enc_sizeof_ev()) == hipSuccess && hipMalloc(&e.evb, nwin * 4) == hipSuccess &&
-            hipMalloc(&e.evt, nwin * 32768 * 8) == hipSuccess && hipMalloc(&e.hnl, r * 2) == hipSuccess &&
-            hipMalloc(&e.evw, nwin * 12) == hipSuccess &&
-            hipMalloc(&e.recdesc, r * enc_sizeof_recdesc()) == hipSuccess && hipMalloc(&e.wl, r * 4) == hipSuccess &&
-            hipMalloc(&e.emisc, 64 * sizeof(uint64_t)) == hipSuccess;
-  if (!ok) { free_enc_scratch(e); return BCW_E_NOMEM; }
-  if (!e.aux && (hipStreamCreateWithFlags(&e.aux, hipStreamNonBlocking) != hipSuccess ||
-                 hipEventCreateWithFlags(&e.ev_scan, hipEventDisableTiming) != hipSuccess ||
-                 hipEventCreateWithFlags(&e.ev_hscan, hipEventDisableTiming) != hipSuccess ||
-                 hipEventCreateWithFlags(&e.ev_desc, hipEventDisableTiming) != hipSuccess))
-    return BCW_E_HIP;
-  (void)hipMemsetAsync(e.mflag, 0, r, c->cur);
-  e.rows_cap = r;
-  return BCW_OK;
-}
-
 int bcw_encode_segment_async(bcw_ctx* c, const uint8_t* d_src, const bcw_encode_params* p,
                              const bcw_record_table* t, const bcw_decode_result* d_src_result, const uint8_t* d_keep,
                              const bcw_encode_out* o, bcw_encode_result* d_result) {
@@ -719,14 +456,12 @@ int bcw_encode_segment_async(bcw_ctx* c, const uint8_t* d_src, const bcw_encode_
   if (p->mode != BCW_ENC_COMPACT && p->mode != BCW_ENC_HINT) return BCW_E_INVAL;
   if (p->hint_pos < BCW_SUPER_BLOCK_SIZE || !o->hint) return BCW_E_INVAL;
   if (p->mode == BCW_ENC_COMPACT && (p->wal_pos < BCW_SUPER_BLOCK_SIZE || !o->wal || !d_keep)) return BCW_E_INVAL;
-  if (!t->foff || !t->size || !t->expire || !t->key_len || !t->val_len || !t->meta_len || !t->first_frag ||
-      !t->emit_frag || !t->hdr_size || !t->flags || !t->etag_off || !t->status)
-    return BCW_E_INVAL;
+  if (!table_has(*t, kColAux)) return BCW_E_INVAL;
   if (!c->s.frags) return BCW_E_INVAL;  // no decode on this context yet
   if (t->capacity >= 0xffffff00ull) return BCW_E_INVAL;  // u32 dense record ids
   DeviceGuard dg(c->device);
   if (!dg.ok) return BCW_E_HIP;
-  int rc = ensure_enc_scratch(c, t->capacity);
+  int rc = enc_scratch_reserve(c, t->capacity);
   if (rc != BCW_OK) return rc;
   EncLaunch L{};
   L.d_src = d_src;
@@ -737,58 +472,51 @@ int bcw_encode_segment_async(bcw_ctx* c, const uint8_t* d_src, const bcw_encode_
   L.d_keep = d_keep;
   L.out = *o;
   L.d_result = d_result;
-  L.frags = c->s.frags;
+  L.frags = c->s.frags.get();
   L.crc_ops = c->tabs.enc_ops;
   L.initc = c->tabs.initc;
   L.num_cus = c->num_cus;
   L.gen = c->frag_gen;
-  return launch_encode(L, c->es, c->cur, &c->prof) == hipSuccess ? BCW_OK : BCW_E_HIP;
+  return launch_encode(L, c->es, c->ea, c->cur, &c->prof) == hipSuccess ? BCW_OK : BCW_E_HIP;
 }
 
 }  // extern "C"
 
 namespace bcw {
-int enc_scratch_reserve(bcw_ctx* c, uint64_t rows) { return ensure_enc_scratch(c, rows); }
+int enc_scratch_reserve(bcw_ctx* c, uint64_t rows) {
+  EncScratch& e = c->es;
+  if (rows <= e.rows_cap && e.emisc) return BCW_OK;
+  (void)hipStreamSynchronize(c->cur);
+  const uint64_t r = std::max(std::max(rows, e.rows_cap), (uint64_t)1);
+  e = EncScratch{};  // frees every array
+  const uint64_t ntiles = r / enc_tile_items() + 2;
+  const uint64_t nwin = r / enc_ev_win() + 2;
+  const bool ok = e.sz.alloc(r * 4) && e.mflag.alloc(r) && e.dsrc.alloc(r * 4) && e.da.alloc((r + 1) * 8) &&
+                  e.hda.alloc((r + 1) * 8) && e.hsz.alloc(r * 4) && e.dpos.alloc(r * 8) && e.hpos.alloc(r * 8) &&
+                  e.tiles.alloc(ntiles * enc_sizeof_tile()) && e.ev.alloc((r + 2) * enc_sizeof_ev()) &&
+                  e.evb.alloc(nwin * 4) && e.evt.alloc(nwin * 32768 * 8) && e.hnl.alloc(r * 2) &&
+                  e.evw.alloc(nwin * 12) && e.recdesc.alloc(r * enc_sizeof_recdesc()) && e.wl.alloc(r * 4) &&
+                  e.emisc.alloc(64 * sizeof(uint64_t));
+  if (!ok) { e = EncScratch{}; return BCW_E_NOMEM; }
+  EncAux& a = c->ea;
+  if (!a.aux && (hipStreamCreateWithFlags(&a.aux, hipStreamNonBlocking) != hipSuccess ||
+                 hipEventCreateWithFlags(&a.ev_scan, hipEventDisableTiming) != hipSuccess ||
+                 hipEventCreateWithFlags(&a.ev_hscan, hipEventDisableTiming) != hipSuccess ||
+                 hipEventCreateWithFlags(&a.ev_desc, hipEventDisableTiming) != hipSuccess))
+    return BCW_E_HIP;
+  (void)hipMemsetAsync(e.mflag.get(), 0, r, c->cur);
+  e.rows_cap = r;
+  return BCW_OK;
+}
 
 // Sync-API staging: the source segment into the context's device buffer, decoded into the context's
 // device table (grown until it holds every record), the fragment scratch retried until it fits.
 int sync_decode(bcw_ctx* c, const uint8_t* h_src, const bcw_decode_params& dp, bcw_decode_result& dres) {
-  uint64_t cap = std::max<uint64_t>(16, dp.seg_len / 64 + 16);
-  if (dp.seg_len > c->d_seg_cap) {
-    (void)hipStreamSynchronize(c->cur);
-    (void)hipFree(c->d_seg);
-    c->d_seg = nullptr;
-    c->d_seg_cap = 0;
-    if (hipMalloc(&c->d_seg, dp.seg_len) != hipSuccess) return BCW_E_NOMEM;
-    c->d_seg_cap = dp.seg_len;
-  }
-  if (dp.seg_len) HIPCHK(hipMemcpyAsync(c->d_seg, h_src, dp.seg_len, hipMemcpyHostToDevice, c->cur));
-  for (;;) {
-    int rc = ensure_dev_table(c, cap, dp.mode == BCW_MODE_HINT);
-    if (rc != BCW_OK) return rc;
-    for (int attempt = 0; attempt < 3; ++attempt) {
-      rc = bcw_decode_segment_async(c, c->d_seg, &dp, &c->d_tab, c->d_result);
-      if (rc != BCW_OK) return rc;
-      HIPCHK(hipMemcpyAsync(&dres, c->d_result, sizeof dres, hipMemcpyDeviceToHost, c->cur));
-      HIPCHK(hipStreamSynchronize(c->cur));
-      if (!dres.retry_frag_capacity) break;
-      if (bcw_ctx_reserve_fragments(c, dres.retry_frag_capacity + 64) != BCW_OK) return BCW_E_CAPACITY;
-    }
-    if (dres.retry_frag_capacity) return BCW_E_NOMEM;
-    if (dres.n_records <= c->d_tab.capacity) return BCW_OK;
-    cap = dres.n_records + 16;
-  }
+  return decode_staged(c, h_src, dp, &dres, std::max<uint64_t>(16, dp.seg_len / 64 + 16), true);
 }
 
 int ensure_keep(bcw_ctx* c, uint64_t rows) {
-  if (rows <= c->d_keep_cap && c->d_keep) return BCW_OK;
-  (void)hipStreamSynchronize(c->cur);
-  (void)hipFree(c->d_keep);
-  c->d_keep = nullptr;
-  c->d_keep_cap = 0;
-  if (hipMalloc(&c->d_keep, std::max<uint64_t>(rows, 1)) != hipSuccess) return BCW_E_NOMEM;
-  c->d_keep_cap = std::max<uint64_t>(rows, 1);
-  return BCW_OK;
+  return c->d_keep.reserve(std::max<uint64_t>(rows, 1), c->cur) ? BCW_OK : BCW_E_NOMEM;
 }
 
 bcw_decode_params src_params(const uint8_t* h_src, const bcw_encode_params* p) {
@@ -807,30 +535,17 @@ bcw_decode_params src_params(const uint8_t* h_src, const bcw_encode_params* p) {
 int encode_run(bcw_ctx* c, const bcw_encode_params* p, const bcw_encode_out* h, bcw_encode_result* h_result,
                bcw_encode_out* d_out) {
   const uint64_t rows = c->d_tab.capacity;
-  const uint64_t need = h->wal_cap + h->hint_cap + rows * 8;
-  if (need > c->d_eout_cap) {
-    (void)hipStreamSynchronize(c->cur);
-    (void)hipFree(c->d_eout);
-    c->d_eout = nullptr;
-    c->d_eout_cap = 0;
-    if (hipMalloc(&c->d_eout, need + 64) != hipSuccess) return BCW_E_NOMEM;
-    c->d_eout_cap = need;
-  }
-  uint8_t* m = (uint8_t*)c->d_eout;
+  Carver measure;
+  carve_encode_out(measure, rows, h->wal_cap, h->hint_cap);
+  if (!c->d_eout.reserve(measure.total(), c->cur)) return BCW_E_NOMEM;
+  Carver cv(c->d_eout.get(), c->d_eout.bytes());
   bcw_encode_out& d = *d_out;
-  d = bcw_encode_out{};
-  d.rec_off = (uint64_t*)m;
-  d.rec_off_cap = rows;
-  m += rows * 8;
-  d.wal = m;
-  d.wal_cap = h->wal_cap;
-  m += (h->wal_cap + 15) & ~15ull;
-  d.hint = (uint8_t*)(((uintptr_t)m + 15) & ~(uintptr_t)15);
-  d.hint_cap = h->hint_cap;
-  if (p->mode == BCW_ENC_HINT && !d.wal) d.wal = d.hint;
-  int rc = bcw_encode_segment_async(c, c->d_seg, p, &c->d_tab, c->d_result, c->d_keep, &d, c->d_eres);
+  d = carve_encode_out(cv, rows, h->wal_cap, h->hint_cap);
+  if (!cv.ok()) return BCW_E_INVAL;
+  int rc = bcw_encode_segment_async(c, c->d_seg.get(), p, &c->d_tab, c->d_result.get(), c->d_keep.get(), &d,
+                                    c->d_eres.get());
   if (rc != BCW_OK) return rc;
-  HIPCHK(hipMemcpyAsync(h_result, c->d_eres, sizeof *h_result, hipMemcpyDeviceToHost, c->cur));
+  HIPCHK(hipMemcpyAsync(h_result, c->d_eres.get(), sizeof *h_result, hipMemcpyDeviceToHost, c->cur));
   HIPCHK(hipStreamSynchronize(c->cur));
   if (!h_result->fits) return BCW_E_CAPACITY;
   if (h->rec_off && h->rec_off_cap < h_result->n_in) return BCW_E_CAPACITY;
@@ -874,9 +589,9 @@ int bcw_encode_segment(bcw_ctx* c, const uint8_t* h_src, const bcw_encode_params
   const uint64_t rows = c->d_tab.capacity;
   rc = ensure_keep(c, rows);  // keep mask (missing entries: dropped)
   if (rc != BCW_OK) return rc;
-  HIPCHK(hipMemsetAsync(c->d_keep, 0, rows, c->cur));
+  HIPCHK(hipMemsetAsync(c->d_keep.get(), 0, rows, c->cur));
   const uint64_t nk = std::min(n_keep, rows);
-  if (h_keep && nk) HIPCHK(hipMemcpyAsync(c->d_keep, h_keep, nk, hipMemcpyHostToDevice, c->cur));
+  if (h_keep && nk) HIPCHK(hipMemcpyAsync(c->d_keep.get(), h_keep, nk, hipMemcpyHostToDevice, c->cur));
   return encode_to_host(c, p, h, h_result, dres);
 }
 
@@ -893,10 +608,10 @@ int bcw_compact_segment(bcw_ctx* c, bcw_index* ix, const uint8_t* h_src, const b
   if (rc != BCW_OK) return rc;
   rc = ensure_keep(c, c->d_tab.capacity);
   if (rc != BCW_OK) return rc;
-  rc = ix_filter_pending(ix, c->d_seg, &dp, &c->d_tab, c->d_result, src_fid, c->d_keep,
-                         h_filter ? c->d_ires : nullptr);
+  rc = ix_filter_pending(ix, c->d_seg.get(), &dp, &c->d_tab, c->d_result.get(), src_fid, c->d_keep.get(),
+                         h_filter ? c->d_ires.get() : nullptr);
   if (rc != BCW_OK) return rc;
-  if (h_filter) HIPCHK(hipMemcpyAsync(h_filter, c->d_ires, sizeof *h_filter, hipMemcpyDeviceToHost, c->cur));
+  if (h_filter) HIPCHK(hipMemcpyAsync(h_filter, c->d_ires.get(), sizeof *h_filter, hipMemcpyDeviceToHost, c->cur));
   rc = encode_to_host(c, p, h, h_result, dres);
   // the rows the index's rules dropped count once the output is final (not for a call refused with BCW_E_CAPACITY)
   return rc != BCW_OK ? rc : ix_rule_commit(ix);
@@ -914,9 +629,10 @@ int bcw_index_recover_segment(bcw_ctx* c, bcw_index* ix, const uint8_t* h_seg, c
   int rc = sync_decode(c, h_seg, *p, dres);
   if (rc != BCW_OK) return rc;
   if (h_dres) *h_dres = dres;
-  rc = bcw_index_put_decoded_async(ix, c->d_seg, p, &c->d_tab, c->d_result, fid, use_record_fid, c->d_ires);
+  rc = bcw_index_put_decoded_async(ix, c->d_seg.get(), p, &c->d_tab, c->d_result.get(), fid, use_record_fid,
+                                   c->d_ires.get());
   if (rc != BCW_OK) return rc;
-  HIPCHK(hipMemcpyAsync(h_out, c->d_ires, sizeof *h_out, hipMemcpyDeviceToHost, c->cur));
+  HIPCHK(hipMemcpyAsync(h_out, c->d_ires.get(), sizeof *h_out, hipMemcpyDeviceToHost, c->cur));
   HIPCHK(hipStreamSynchronize(c->cur));
   return BCW_OK;
 }

@@ -1700,23 +1700,24 @@ hipError_t launch_decode(const uint8_t* d_seg, const bcw_decode_params& p, const
   // dispatcher then starts every k_crc on the same XCD, so each workgroup class (blockIdx % 8, XBal) keeps its XCD
   // from decode to decode
   const uint32_t nb_grid = (uint32_t)(((nblocks + 63) / 64 + 7) / 8 * 8);
-  const EmitArgs ea{d_seg, p.seg_len, p, s.frags, s.fbase, s.rbase, s.bsum, t, s.misc, 0u, nullptr};
+  const EmitArgs ea{d_seg, p.seg_len, p, s.frags.get(), s.fbase.get(), s.rbase.get(), s.bsum.get(), t, s.misc.get(),
+                    0u, nullptr};
   pr.begin(K_CHASE, stream, ev);
-  k_chase<0><<<nb_grid, kChaseWaves * 64, 0, stream>>>(d_seg, p.seg_len, p.start_off, nblocks, s.fbase, s.rbase, s.bsum, s.frags,
-                                        s.srec, s.frag_cap, s.lb, s.lbe, s.misc, s.epoch, tabs.initc, s.chase_direct,
-                                        s.test_abort_wg, s.wstart, (uint32_t)num_cus * kCrcWaves, s.xbal, s.xbal_on);
+  k_chase<0><<<nb_grid, kChaseWaves * 64, 0, stream>>>(
+      d_seg, p.seg_len, p.start_off, nblocks, s.fbase.get(), s.rbase.get(), s.bsum.get(), s.frags.get(), s.srec.get(),
+      s.frag_cap, s.lb.get(), s.lbe.get(), s.misc.get(), s.epoch, tabs.initc, s.chase_direct, s.test_abort_wg,
+      s.wstart.get(), (uint32_t)num_cus * kCrcWaves, s.xbal.get(), s.xbal_on);
   s.test_abort_wg = 0;
   pr.end(K_CHASE, stream, ev);
   if ((++s.epoch & 0xffffffull) == 0) {  // 24-bit look-back epochs: clear the words before reuse
-    (void)hipMemsetAsync(s.lb, 0, s.nlb * sizeof(uint64_t), stream);
-    (void)hipMemsetAsync(s.lbe, 0, s.nlb * sizeof(uint64_t), stream);
+    (void)hipMemsetAsync(s.lb.get(), 0, s.nlb * sizeof(uint64_t), stream);
+    (void)hipMemsetAsync(s.lbe.get(), 0, s.nlb * sizeof(uint64_t), stream);
     s.epoch = 1;
   }
   pr.begin(K_CRC, stream, ev);
-  k_crc<0><<<(uint32_t)num_cus, kCrcThreads, 0, stream>>>(d_seg, p.seg_len, p.start_off, nblocks, s.fbase, s.fok,
-                                                         s.srec, s.frag_cap, tabs, ea,
-                                                         tail_panic, gen, d_result, s.misc, 0ull, nblocks,
-                                                         (uint32_t)num_cus, s.wstart, s.xbal);
+  k_crc<0><<<(uint32_t)num_cus, kCrcThreads, 0, stream>>>(
+      d_seg, p.seg_len, p.start_off, nblocks, s.fbase.get(), s.fok.get(), s.srec.get(), s.frag_cap, tabs, ea, tail_panic,
+      gen, d_result, s.misc.get(), 0ull, nblocks, (uint32_t)num_cus, s.wstart.get(), s.xbal.get());
   pr.end(K_CRC, stream, ev);
   return hipGetLastError();
 }
@@ -1724,8 +1725,8 @@ hipError_t launch_decode(const uint8_t* d_seg, const bcw_decode_params& p, const
 hipError_t launch_export_frags(const Scratch& s, const bcw_frag_table& out, uint32_t start_off, hipStream_t stream,
                                uint64_t n, const uint32_t* initc) {
   if (n == 0) return hipSuccess;
-  k_export_frags<<<(uint32_t)((n + 255) / 256), 256, 0, stream>>>(s.frags, s.fok, s.misc, s.frag_cap, start_off, out,
-                                                                    initc);
+  k_export_frags<<<(uint32_t)((n + 255) / 256), 256, 0, stream>>>(s.frags.get(), s.fok.get(), s.misc.get(),
+                                                                    s.frag_cap, start_off, out, initc);
   return hipGetLastError();
 }
 

@@ -39,7 +39,7 @@
 
 #include "bcw_crc_dev.h"
 #include "bcw_frame.h"
-#include "bcw_internal.h"
+#include "bcw_host.h"
 
 namespace bcw {
 namespace enc {
@@ -66,7 +66,7 @@ enum {
 };
 constexpr int kLayStride = 8;
 static_assert(kXNin == X_NIN && kXErr == X_ERR && kXNDense == X_NDENSE && kXLay == X_LAY && kXPut >= X_LAY + 2 * kLayStride,
-              "emisc slots exported through bcw_internal.h");
+              "emisc slots exported through bcw_host.h");
 
 // A_{8m}(x) (m zero bytes appended to a raw CRC-32C state) from the power-of-two operators p2[k] =
 // A_{8*2^k} (or their inverses: A_{8m}^-1), one operator per set bit of m
@@ -889,7 +889,7 @@ struct WArgs {
   WLay w[2];              // dst WAL and hint WAL of a compaction (nlay = 2), or the hint WAL
   uint32_t nlay;
   const uint64_t* emisc;
-  const uint32_t* wops;   // enc_ops (layout in bcw_internal.h)
+  const uint32_t* wops;   // enc_ops (layout in bcw_crc_consts.h)
   const uint32_t* initc;  // A_{8L}(0xFFFFFFFF)
   uint32_t abl;           // measurement-only ablations of k_wcopy (BCW_ENC_ABL bits 4/8/16); 0 in the product
   uint32_t* wl;           // [rows] k_wcopy's leftover dst records: k_write<16>'s from the front, k_write_general's
@@ -1729,39 +1729,40 @@ __global__ void k_enc_finalize(const uint64_t* __restrict__ emisc, uint32_t mode
 static void launch_scan(EncScratch& s, uint64_t rows, const uint32_t* sz, int over_rows, int lay, uint64_t* da,
                         hipStream_t st) {
   using namespace enc;
-  TileSum* tiles = static_cast<TileSum*>(s.tiles);
+  TileSum* tiles = static_cast<TileSum*>(s.tiles.get());
   const uint32_t ntiles = (uint32_t)((rows + kTileItems - 1) / kTileItems) + 1;
-  k_tile_sums<<<ntiles, 256, 0, st>>>(sz, s.emisc, over_rows, tiles);
-  k_tile_scan<<<1, 1024, 0, st>>>(tiles, s.emisc, over_rows, lay, da);
-  k_tile_scatter<<<ntiles, 256, 0, st>>>(sz, s.emisc, over_rows, tiles, s.dsrc, da);
+  k_tile_sums<<<ntiles, 256, 0, st>>>(sz, s.emisc.get(), over_rows, tiles);
+  k_tile_scan<<<1, 1024, 0, st>>>(tiles, s.emisc.get(), over_rows, lay, da);
+  k_tile_scatter<<<ntiles, 256, 0, st>>>(sz, s.emisc.get(), over_rows, tiles, s.dsrc.get(), da);
 }
 // ... and the event scan from file position pos
 static void launch_events(EncScratch& s, uint64_t rows, int lay, const uint64_t* da, uint64_t pos, hipStream_t st) {
   using namespace enc;
-  Ev* evs = static_cast<Ev*>(s.ev);
+  Ev* evs = static_cast<Ev*>(s.ev.get());
   const uint32_t nwin = (uint32_t)(rows / kEvWin + 1);
-  k_ev_win<<<nwin, 1024, 0, st>>>(da, s.emisc, lay, pos - 40, s.evt, s.hnl);
-  k_ev_walk<<<1, 64, 0, st>>>(s.emisc, lay, pos - 40, s.evt, s.evw, evs);
-  k_ev_emit<<<(nwin + 63) / 64, 64, 0, st>>>(da, s.emisc, s.evw, s.hnl, evs, s.evb);
-  k_ev_fix<<<1, 1024, 0, st>>>(da, s.emisc, lay, evs);
+  k_ev_win<<<nwin, 1024, 0, st>>>(da, s.emisc.get(), lay, pos - 40, s.evt.get(), s.hnl.get());
+  k_ev_walk<<<1, 64, 0, st>>>(s.emisc.get(), lay, pos - 40, s.evt.get(), s.evw.get(), evs);
+  k_ev_emit<<<(nwin + 63) / 64, 64, 0, st>>>(da, s.emisc.get(), s.evw.get(), s.hnl.get(), evs, s.evb.get());
+  k_ev_fix<<<1, 1024, 0, st>>>(da, s.emisc.get(), lay, evs);
 }
 
 void enc_layout_reset(EncScratch& s, hipStream_t st) {
-  (void)hipMemsetAsync(s.emisc, 0, 64 * sizeof(uint64_t), st);
-  (void)hipMemsetAsync(s.emisc + enc::X_ERR, 0xff, sizeof(uint64_t), st);
+  (void)hipMemsetAsync(s.emisc.get(), 0, 64 * sizeof(uint64_t), st);
+  (void)hipMemsetAsync(s.emisc.get() + enc::X_ERR, 0xff, sizeof(uint64_t), st);
 }
 
 hipError_t enc_layout_run(EncScratch& s, uint64_t rows, uint64_t wal_pos, hipStream_t st) {
   using namespace enc;
-  launch_scan(s, rows, s.sz, 1, 0, s.da, st);
-  launch_events(s, rows, 0, s.da, wal_pos, st);
-  k_recoff<<<(uint32_t)((rows + 255) / 256) + 1, 256, 0, st>>>(s.da, s.dsrc, s.emisc, 0, static_cast<Ev*>(s.ev), s.evb,
-                                                               s.dpos, nullptr);
+  launch_scan(s, rows, s.sz.get(), 1, 0, s.da.get(), st);
+  launch_events(s, rows, 0, s.da.get(), wal_pos, st);
+  k_recoff<<<(uint32_t)((rows + 255) / 256) + 1, 256, 0, st>>>(s.da.get(), s.dsrc.get(), s.emisc.get(), 0,
+                                                               static_cast<Ev*>(s.ev.get()), s.evb.get(), s.dpos.get(),
+                                                               nullptr);
   return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------
-hipError_t launch_encode(const EncLaunch& L, EncScratch& s, hipStream_t st, Prof* prof) {
+hipError_t launch_encode(const EncLaunch& L, EncScratch& s, EncAux& a, hipStream_t st, Prof* prof) {
   using namespace enc;
   Prof dummy;
   Prof& pr = prof ? *prof : dummy;
@@ -1782,10 +1783,12 @@ hipError_t launch_encode(const EncLaunch& L, EncScratch& s, hipStream_t st, Prof
   e.gen = L.gen;
   const uint64_t rows = L.rows;
   const bool compact = L.p.mode == BCW_ENC_COMPACT;
-  Ev* evs = static_cast<Ev*>(s.ev);
+  Ev* evs = static_cast<Ev*>(s.ev.get());
   enc_layout_reset(s, st);
   pr.begin(K_ENC_PREP, st, ev0);
-  if (rows) k_enc_prep<<<(uint32_t)((rows + 255) / 256), 256, 0, st>>>(e, rows, s.sz, s.mflag, L.out.rec_off, s.emisc);
+  if (rows)
+    k_enc_prep<<<(uint32_t)((rows + 255) / 256), 256, 0, st>>>(e, rows, s.sz.get(), s.mflag.get(), L.out.rec_off,
+                                                               s.emisc.get());
   pr.end(K_ENC_PREP, st, ev0);
   auto scan = [&](const uint32_t* sz, int over_rows, int lay, uint64_t* da) {
     launch_scan(s, rows, sz, over_rows, lay, da, st);
@@ -1793,13 +1796,13 @@ hipError_t launch_encode(const EncLaunch& L, EncScratch& s, hipStream_t st, Prof
 
   WArgs W{};
   W.e = e;
-  W.emisc = s.emisc;
+  W.emisc = s.emisc.get();
   W.wops = L.crc_ops;
   W.initc = L.initc;
   static const int abl_env = [] { const char* v = getenv("BCW_ENC_ABL"); return v ? atoi(v) : 0; }();
   W.abl = (uint32_t)abl_env;
   const uint32_t rgrid = (uint32_t)((rows + 255) / 256) + 1;
-  RecDescW* wd = static_cast<RecDescW*>(s.recdesc);
+  RecDescW* wd = static_cast<RecDescW*>(s.recdesc.get());
   // persistent write grid: as many workgroups per CU as are resident
   auto wgrid = [&](int g) {
     static int n = 0;
@@ -1820,28 +1823,30 @@ hipError_t launch_encode(const EncLaunch& L, EncScratch& s, hipStream_t st, Prof
     // stream st: the layouts and the writers; stream aux: the dst records' payload descriptors (after the
     // dense scan), built while the layouts run
     pr.begin(K_ENC_SCAN, st, ev0);
-    scan(s.sz, 1, 0, s.da);
+    scan(s.sz.get(), 1, 0, s.da.get());
     pr.end(K_ENC_SCAN, st, ev0);
-    (void)hipEventRecord(s.ev_scan, st);
-    (void)hipStreamWaitEvent(s.aux, s.ev_scan, 0);
-    k_recdesc_w<PM_DST><<<rgrid, 256, 0, s.aux>>>(e, s.emisc, s.dsrc, nullptr, nullptr, s.mflag, L.crc_ops, wd);
-    (void)hipEventRecord(s.ev_desc, s.aux);
-    layout(0, s.da, L.p.wal_pos);
-    k_recoff<<<rgrid, 256, 0, st>>>(s.da, s.dsrc, s.emisc, 0, evs, s.evb, s.dpos, L.out.rec_off);
+    (void)hipEventRecord(a.ev_scan, st);
+    (void)hipStreamWaitEvent(a.aux, a.ev_scan, 0);
+    k_recdesc_w<PM_DST><<<rgrid, 256, 0, a.aux>>>(e, s.emisc.get(), s.dsrc.get(), nullptr, nullptr, s.mflag.get(),
+                                                  L.crc_ops, wd);
+    (void)hipEventRecord(a.ev_desc, a.aux);
+    layout(0, s.da.get(), L.p.wal_pos);
+    k_recoff<<<rgrid, 256, 0, st>>>(s.da.get(), s.dsrc.get(), s.emisc.get(), 0, evs, s.evb.get(), s.dpos.get(),
+                                    L.out.rec_off);
     // the hint WAL's layout needs the dst offsets (its records carry them)
     pr.begin(K_ENC_HINT_LAYOUT, st, ev0);
-    k_hint_sizes<<<rgrid, 256, 0, st>>>(e, s.emisc, s.dsrc, s.da, s.dpos, s.hsz);
-    scan(s.hsz, 0, 1, s.hda);
+    k_hint_sizes<<<rgrid, 256, 0, st>>>(e, s.emisc.get(), s.dsrc.get(), s.da.get(), s.dpos.get(), s.hsz.get());
+    scan(s.hsz.get(), 0, 1, s.hda.get());
     pr.end(K_ENC_HINT_LAYOUT, st, ev0);
-    layout(1, s.hda, L.p.hint_pos);
-    k_recoff<<<rgrid, 256, 0, st>>>(s.hda, s.dsrc, s.emisc, 1, evs, s.evb, s.hpos, nullptr);
-    (void)hipStreamWaitEvent(st, s.ev_desc, 0);
-    W.w[0] = WLay{s.da, s.dpos, wd, L.out.wal, L.p.wal_pos, L.out.wal_cap, 0};
-    W.w[1] = WLay{s.hda, s.hpos, nullptr, L.out.hint, L.p.hint_pos, L.out.hint_cap, 1};
+    layout(1, s.hda.get(), L.p.hint_pos);
+    k_recoff<<<rgrid, 256, 0, st>>>(s.hda.get(), s.dsrc.get(), s.emisc.get(), 1, evs, s.evb.get(), s.hpos.get(), nullptr);
+    (void)hipStreamWaitEvent(st, a.ev_desc, 0);
+    W.w[0] = WLay{s.da.get(), s.dpos.get(), wd, L.out.wal, L.p.wal_pos, L.out.wal_cap, 0};
+    W.w[1] = WLay{s.hda.get(), s.hpos.get(), nullptr, L.out.hint, L.p.hint_pos, L.out.hint_cap, 1};
     W.nlay = 1;
-    W.wl = s.wl;
+    W.wl = s.wl.get();
     W.rows = rows;
-    W.wcnt = s.emisc + X_WL16;
+    W.wcnt = s.emisc.get() + X_WL16;
     const int abl = abl_env & 3;
     pr.begin(K_ENC_WRITE, st, ev0);
     // measurement-only ablation (BCW_ENC_ABL: 1 = dst WAL only, 2 = hint WAL only); 0 in the product
@@ -1856,25 +1861,25 @@ hipError_t launch_encode(const EncLaunch& L, EncScratch& s, hipStream_t st, Prof
       k_wcopy<<<(uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((rows + 3) / 4, (uint64_t)L.num_cus * s.wcopy_resident)), kCT, 0,
                 st>>>(W);
       k_write<16><<<wgrid(16), kWT, 0, st>>>(W);
-      k_write_general<PM_DST><<<std::min<uint32_t>(rgrid, (uint32_t)L.num_cus * 4), 256, 0, st>>>(W, 0, s.dsrc, nullptr,
-                                                                                            nullptr, s.mflag);
+      k_write_general<PM_DST><<<std::min<uint32_t>(rgrid, (uint32_t)L.num_cus * 4), 256, 0, st>>>(
+          W, 0, s.dsrc.get(), nullptr, nullptr, s.mflag.get());
     }
-    if (abl != 1) k_hwrite<PM_HINT_DST><<<rgrid, 256, 0, st>>>(W, 1, s.dsrc, s.da, s.dpos);
+    if (abl != 1) k_hwrite<PM_HINT_DST><<<rgrid, 256, 0, st>>>(W, 1, s.dsrc.get(), s.da.get(), s.dpos.get());
     pr.end(K_ENC_WRITE, st, ev0);
   } else {
     pr.begin(K_ENC_SCAN, st, ev0);
-    scan(s.sz, 1, 0, s.hda);
+    scan(s.sz.get(), 1, 0, s.hda.get());
     pr.end(K_ENC_SCAN, st, ev0);
-    layout(0, s.hda, L.p.hint_pos);
-    k_recoff<<<rgrid, 256, 0, st>>>(s.hda, s.dsrc, s.emisc, 0, evs, s.evb, s.hpos, nullptr);
-    W.w[0] = WLay{s.hda, s.hpos, nullptr, L.out.hint, L.p.hint_pos, L.out.hint_cap, 0};
+    layout(0, s.hda.get(), L.p.hint_pos);
+    k_recoff<<<rgrid, 256, 0, st>>>(s.hda.get(), s.dsrc.get(), s.emisc.get(), 0, evs, s.evb.get(), s.hpos.get(), nullptr);
+    W.w[0] = WLay{s.hda.get(), s.hpos.get(), nullptr, L.out.hint, L.p.hint_pos, L.out.hint_cap, 0};
     W.w[1] = W.w[0];
     W.nlay = 1;
     pr.begin(K_ENC_WRITE, st, ev0);
-    k_hwrite<PM_HINT_SRC><<<rgrid, 256, 0, st>>>(W, 0, s.dsrc, nullptr, nullptr);
+    k_hwrite<PM_HINT_SRC><<<rgrid, 256, 0, st>>>(W, 0, s.dsrc.get(), nullptr, nullptr);
     pr.end(K_ENC_WRITE, st, ev0);
   }
-  k_enc_finalize<<<1, 1, 0, st>>>(s.emisc, L.p.mode, L.p.wal_pos, L.out.wal_cap, L.p.hint_pos, L.out.hint_cap,
+  k_enc_finalize<<<1, 1, 0, st>>>(s.emisc.get(), L.p.mode, L.p.wal_pos, L.out.wal_cap, L.p.hint_pos, L.out.hint_cap,
                                   L.d_src_result, L.d_result);
   return hipGetLastError();
 }

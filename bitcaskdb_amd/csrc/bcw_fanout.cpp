@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "bcw.h"
-#include "bcw_internal.h"
+#include "bcw_host.h"
 
 using namespace bcw;
 
@@ -243,17 +243,8 @@ int bcw_compact_wals(bcw_index* ix, bcw_ctx* const* ctxs, uint32_t n_ctx, const 
     Staging stg;
     Entries mine;
     uint64_t staged[3] = {0, 0, 0};  // the staging index's rule counts so far
-    uint64_t* d_cnt = nullptr;  // (direct) the filter's counters
-    struct FreeCnt {
-      bcw_ctx* c;
-      uint64_t*& p;
-      ~FreeCnt() {
-        if (p) {
-          DeviceGuard dg(c->device);
-          (void)hipFree(p);
-        }
-      }
-    } free_cnt{c, d_cnt};
+    DeviceGuard on_dev(c->device);  // this thread works on c's device; d_cnt is freed there
+    DevBuf<uint64_t> d_cnt;         // (direct) the filter's counters
     for (uint64_t k = w; k < n_src; k += n_ctx) {
       const bcw_compact_src& S = srcs[k];
       bcw_encode_params p = *dst;
@@ -267,7 +258,7 @@ int bcw_compact_wals(bcw_index* ix, bcw_ctx* const* ctxs, uint32_t n_ctx, const 
       int r = BCW_OK;
       if (direct && !d_cnt) {
         DeviceGuard dg(c->device);
-        r = dg.ok && hipMalloc(&d_cnt, kIxCounters * sizeof(uint64_t)) == hipSuccess ? BCW_OK : BCW_E_HIP;
+        r = dg.ok && d_cnt.alloc(kIxCounters * sizeof(uint64_t)) ? BCW_OK : BCW_E_HIP;
       }
       if (!direct) {
         const bool fresh = !stg.ix;
@@ -298,14 +289,15 @@ int bcw_compact_wals(bcw_index* ix, bcw_ctx* const* ctxs, uint32_t n_ctx, const 
         r = dg.ok ? sync_decode(c, S.data, dp, dres) : BCW_E_HIP;
         if (r == BCW_OK) r = ensure_keep(c, c->d_tab.capacity);
         if (r == BCW_OK)
-          r = direct ? ix_filter_on(ix, c, c->d_seg, &dp, &c->d_tab, c->d_result, S.fid, c->d_keep, d_cnt, c->d_ires)
-                     : bcw_compact_filter_async(stg.ix, c->d_seg, &dp, &c->d_tab, c->d_result, S.fid, c->d_keep,
-                                                c->d_ires);
+          r = direct ? ix_filter_on(ix, c, c->d_seg.get(), &dp, &c->d_tab, c->d_result.get(), S.fid, c->d_keep.get(),
+                                    d_cnt.get(), c->d_ires.get())
+                     : bcw_compact_filter_async(stg.ix, c->d_seg.get(), &dp, &c->d_tab, c->d_result.get(), S.fid,
+                                                c->d_keep.get(), c->d_ires.get());
         if (r == BCW_OK && direct && ruled_on &&
-            hipMemcpyAsync(&ruled[3 * k], d_cnt + kIxRuleCnt, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->cur) !=
+            hipMemcpyAsync(&ruled[3 * k], d_cnt.get() + kIxRuleCnt, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->cur) !=
                 hipSuccess)
           r = BCW_E_HIP;
-        if (r == BCW_OK && (hipMemcpyAsync(&filt[k], c->d_ires, sizeof filt[k], hipMemcpyDeviceToHost, c->cur) !=
+        if (r == BCW_OK && (hipMemcpyAsync(&filt[k], c->d_ires.get(), sizeof filt[k], hipMemcpyDeviceToHost, c->cur) !=
                                 hipSuccess ||
                             hipStreamSynchronize(c->cur) != hipSuccess))
           r = BCW_E_HIP;

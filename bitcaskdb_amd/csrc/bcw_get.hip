@@ -17,15 +17,15 @@
 #include <new>
 #include <vector>
 
-#include "bcw_internal.h"
+#include "bcw_host.h"
 #include "bcw_read_body.h"
 
 struct bcw_walset {
   bcw_ctx* ctx = nullptr;
   bcw::WalTable t;
-  bcw::WalEnt* d_ents = nullptr;  // the device copy of t.ents
+  bcw::DevBuf<bcw::WalEnt> d_ents;  // the device copy of t.ents ([d_cap])
   uint64_t d_cap = 0;
-  uint64_t* d_blk = nullptr;      // [2 * blk_cap] per lookup workgroup: slot sums, then found counts
+  bcw::DevBuf<uint64_t> d_blk;      // [2 * blk_cap] per lookup workgroup: slot sums, then found counts
   uint64_t blk_cap = 0;
 };
 
@@ -169,14 +169,13 @@ int ws_publish(bcw_walset* ws) {
   const uint64_t n = ws->t.ents.size();
   if (n > ws->d_cap) {
     const uint64_t cap = std::max<uint64_t>(16, std::max(n, ws->d_cap * 2));
-    WalEnt* d = nullptr;
-    if (hipMalloc(&d, cap * sizeof(WalEnt)) != hipSuccess) return BCW_E_NOMEM;
+    DevBuf<WalEnt> d;  // the new one first: the old copy stays valid when there is no room
+    if (!d.alloc(cap * sizeof(WalEnt))) return BCW_E_NOMEM;
     (void)hipStreamSynchronize(st);
-    (void)hipFree(ws->d_ents);
-    ws->d_ents = d;
+    ws->d_ents = std::move(d);
     ws->d_cap = cap;
   }
-  if (n && hipMemcpyAsync(ws->d_ents, ws->t.ents.data(), n * sizeof(WalEnt), hipMemcpyHostToDevice, st) != hipSuccess)
+  if (n && hipMemcpyAsync(ws->d_ents.get(), ws->t.ents.data(), n * sizeof(WalEnt), hipMemcpyHostToDevice, st) != hipSuccess)
     return BCW_E_HIP;
   // the host table may change again as soon as this returns
   return hipStreamSynchronize(st) == hipSuccess ? BCW_OK : BCW_E_HIP;
@@ -201,11 +200,6 @@ int ws_put(bcw_walset* ws, const WalEnt& e, void* own) {
   return rc;
 }
 
-bool table_ok(const bcw_record_table& t) {
-  return !t.status || (t.foff && t.size && t.expire && t.key_len && t.val_len && t.meta_len && t.hdr_size && t.flags &&
-                       t.etag_off);
-}
-
 }  // namespace
 
 extern "C" {
@@ -225,8 +219,6 @@ int bcw_walset_destroy(bcw_walset* ws) {
   DeviceGuard dg(ws->ctx->device);
   (void)hipStreamSynchronize(ws->ctx->cur);
   for (void* img : ws->t.owned) (void)hipFree(img);
-  (void)hipFree(ws->d_ents);
-  (void)hipFree(ws->d_blk);
   delete ws;
   return BCW_OK;
 }
@@ -274,7 +266,7 @@ int bcw_get_records_async(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p
   const bcw_get_out& o = *d_out;
   if (n && (!d_key_off || !o.get_status || !o.rd_status || !o.fid || !o.off || !o.size || !o.pay_off))
     return BCW_E_INVAL;
-  if ((o.payload_cap && !o.payload) || !table_ok(o.table)) return BCW_E_INVAL;
+  if ((o.payload_cap && !o.payload) || !read_table_ok(o.table)) return BCW_E_INVAL;
   bcw_ctx* c = ws->ctx;
   DeviceGuard dg(c->device);
   if (!dg.ok) return BCW_E_HIP;
@@ -282,20 +274,19 @@ int bcw_get_records_async(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p
   const uint64_t nb = (n + kGetLookupKeys - 1) / kGetLookupKeys;
   if (nb > ws->blk_cap) {
     const uint64_t cap = std::max<uint64_t>(1024, std::max(nb, ws->blk_cap * 2));
-    uint64_t* d = nullptr;
-    if (hipMalloc(&d, 2 * cap * sizeof(uint64_t)) != hipSuccess) return BCW_E_NOMEM;
+    DevBuf<uint64_t> d;
+    if (!d.alloc(2 * cap * sizeof(uint64_t))) return BCW_E_NOMEM;
     (void)hipStreamSynchronize(st);
-    (void)hipFree(ws->d_blk);
-    ws->d_blk = d;
+    ws->d_blk = std::move(d);
     ws->blk_cap = cap;
   }
-  uint64_t* bsum = ws->d_blk;
-  uint64_t* bfound = ws->d_blk + ws->blk_cap;
+  uint64_t* bsum = ws->d_blk.get();
+  uint64_t* bfound = bsum + ws->blk_cap;
   Prof* prof = &c->prof;
   hipEvent_t ev = nullptr;
 
   GetLookup g{};
-  g.wals = ws->d_ents;
+  g.wals = ws->d_ents.get();
   g.n_wals = (uint32_t)ws->t.ents.size();
   g.n = n;
   g.keys = d_keys;
@@ -315,7 +306,7 @@ int bcw_get_records_async(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p
   if (n == 0) return BCW_OK;
 
   get::ReadArgs A{};
-  A.wals = ws->d_ents;
+  A.wals = ws->d_ents.get();
   A.n_wals = g.n_wals;
   A.p = *p;
   A.n = n;
@@ -339,7 +330,7 @@ int bcw_get_records(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p, uint
   const bcw_get_out& h = *h_out;
   if (n && (!h_key_off || !h.get_status || !h.rd_status || !h.fid || !h.off || !h.size || !h.pay_off))
     return BCW_E_INVAL;
-  if ((h.payload_cap && !h.payload) || !table_ok(h.table)) return BCW_E_INVAL;
+  if ((h.payload_cap && !h.payload) || !read_table_ok(h.table)) return BCW_E_INVAL;
   *h_result = bcw_get_result{};
   h_result->fits = 1;
   if (n == 0) return BCW_OK;
@@ -351,76 +342,32 @@ int bcw_get_records(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p, uint
   DeviceGuard dg(c->device);
   if (!dg.ok) return BCW_E_HIP;
   const bool tab = h.table.status != nullptr;
-  const uint64_t kbp = (kb + 15) & ~15ull, pcap = (h.payload_cap + 15) & ~15ull;
-  // keys | payload | key_off, fid, off, size, pay_off (8 B) | table (3 x 8 + 5 x 4 + 4 x 1 = 48 B per row) | the two
-  // status columns | result (aligned up to 16)
-  const uint64_t bytes = kbp + pcap + 8 * (n + 1) + 32 * n + (tab ? 48 * n : 0) + 2 * n + sizeof(bcw_get_result) + 64;
-  void* mem = nullptr;
-  if (hipMalloc(&mem, bytes) != hipSuccess) return BCW_E_NOMEM;
-  uint8_t* m = (uint8_t*)mem;
-  uint8_t* d_keys = m; m += kbp;
-  bcw_get_out d{};
-  d.payload = m; m += pcap;
-  d.payload_cap = h.payload_cap;
-  uint64_t* d_koff = (uint64_t*)m; m += 8 * (n + 1);
-  d.fid = (uint64_t*)m; m += 8 * n;
-  d.off = (uint64_t*)m; m += 8 * n;
-  d.size = (uint64_t*)m; m += 8 * n;
-  d.pay_off = (uint64_t*)m; m += 8 * n;
-  bcw_record_table& dt = d.table;
-  if (tab) {
-    dt.capacity = n;
-    dt.foff = (uint64_t*)m; m += 8 * n;
-    dt.size = (uint64_t*)m; m += 8 * n;
-    dt.expire = (uint64_t*)m; m += 8 * n;
-    dt.key_len = (uint32_t*)m; m += 4 * n;
-    dt.val_len = (uint32_t*)m; m += 4 * n;
-    dt.meta_len = (uint32_t*)m; m += 4 * n;
-    dt.first_frag = (uint32_t*)m; m += 4 * n;
-    dt.emit_frag = (uint32_t*)m; m += 4 * n;
-    dt.hdr_size = m; m += n;
-    dt.flags = m; m += n;
-    dt.etag_off = m; m += n;
-    dt.status = m; m += n;
-  }
-  d.get_status = m; m += n;
-  d.rd_status = m; m += n;
-  bcw_get_result* d_res = (bcw_get_result*)(((uintptr_t)m + 15) & ~(uintptr_t)15);
-  if ((uint8_t*)(d_res + 1) > (uint8_t*)mem + bytes) {  // the carve-up above must stay inside the allocation
-    (void)hipFree(mem);
-    return BCW_E_INVAL;
-  }
+  DevBuf<> mem;
+  GetLayout L;
+  if (const int rc = carve_alloc(mem, [&](Carver& cv) { L = carve_get(cv, kb, h.payload_cap, n, tab); })) return rc;
+  const bcw_get_out& d = L.out;
   hipStream_t st = c->cur;
   std::vector<uint64_t> koff(n + 1);
   for (uint64_t i = 0; i <= n; ++i) koff[i] = h_key_off[i] - h_key_off[0];
   auto down = [&](void* dst, const void* src, uint64_t b) {
     return !dst || b == 0 || hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, st) == hipSuccess;
   };
-  bool ok = (kb == 0 || hipMemcpyAsync(d_keys, h_keys + h_key_off[0], kb, hipMemcpyHostToDevice, st) == hipSuccess) &&
-            hipMemcpyAsync(d_koff, koff.data(), 8 * (n + 1), hipMemcpyHostToDevice, st) == hipSuccess;
-  int rc = ok ? bcw_get_records_async(ix, ws, p, n, d_keys, d_koff, &d, d_res) : BCW_E_HIP;
+  bool ok = (kb == 0 || hipMemcpyAsync(L.keys, h_keys + h_key_off[0], kb, hipMemcpyHostToDevice, st) == hipSuccess) &&
+            hipMemcpyAsync(L.key_off, koff.data(), 8 * (n + 1), hipMemcpyHostToDevice, st) == hipSuccess;
+  int rc = ok ? bcw_get_records_async(ix, ws, p, n, L.keys, L.key_off, &d, L.res) : BCW_E_HIP;
   if (rc == BCW_OK) {
-    ok = down(h_result, d_res, sizeof(bcw_get_result)) && down(h.get_status, d.get_status, n) &&
+    ok = down(h_result, L.res, sizeof(bcw_get_result)) && down(h.get_status, d.get_status, n) &&
          down(h.rd_status, d.rd_status, n) && down(h.fid, d.fid, 8 * n) && down(h.off, d.off, 8 * n) &&
          down(h.size, d.size, 8 * n) && down(h.pay_off, d.pay_off, 8 * n) && hipStreamSynchronize(st) == hipSuccess;
     rc = !ok ? BCW_E_HIP : h_result->fits ? BCW_OK : BCW_E_CAPACITY;
   }
   if (rc == BCW_OK) {
     ok = down(h.payload, d.payload, h_result->payload_need);
-    if (ok && tab) {
-      const uint64_t k = std::min(n, h.table.capacity);
-      const bcw_record_table& t = h.table;
-      ok = down(t.foff, dt.foff, 8 * k) && down(t.size, dt.size, 8 * k) && down(t.expire, dt.expire, 8 * k) &&
-           down(t.key_len, dt.key_len, 4 * k) && down(t.val_len, dt.val_len, 4 * k) &&
-           down(t.meta_len, dt.meta_len, 4 * k) && down(t.first_frag, dt.first_frag, 4 * k) &&
-           down(t.emit_frag, dt.emit_frag, 4 * k) && down(t.hdr_size, dt.hdr_size, k) && down(t.flags, dt.flags, k) &&
-           down(t.etag_off, dt.etag_off, k) && down(t.status, dt.status, k);
-    }
+    if (ok && tab) ok = table_copy_down(h.table, d.table, std::min(n, h.table.capacity), st);
     ok = ok && hipStreamSynchronize(st) == hipSuccess;
     if (!ok) rc = BCW_E_HIP;
   }
-  (void)hipStreamSynchronize(st);
-  (void)hipFree(mem);
+  (void)hipStreamSynchronize(st);  // before mem goes
   return rc;
 }
 

@@ -41,7 +41,7 @@
 
 #include "bcw_crc_dev.h"
 #include "bcw_drop.h"
-#include "bcw_internal.h"
+#include "bcw_host.h"
 #include "bcw_murmur.h"
 #include "bcw_read_body.h"
 #include "bcw_rules.h"
@@ -1108,13 +1108,10 @@ struct bcw_index {
   uint64_t seq_base = 1;                // sequence number of the next op
   uint64_t limited = 0;                 // the capacity bound (bcw_index_set_limit; 0: none)
   // per-op scratch
-  uint64_t* op_kref = nullptr;
-  uint64_t* op_hash = nullptr;
-  uint64_t* op_slot = nullptr;
+  DevBuf<uint64_t> op_kref, op_hash, op_slot;  // [op_cap] each
   uint64_t op_cap = 0;
   // host-batch staging (device copies)
-  void* stage = nullptr;
-  uint64_t stage_cap = 0;
+  DevBuf<> stage;
   bcw_index_result* d_res = nullptr;
   // compaction filter rules (bcw_index_set_compact_rules): the host copy (mask 0: none; the prefix arrays point into
   // the two vectors), the packed prefix table and the counters on the device (allocated with the first rules: three
@@ -1131,7 +1128,7 @@ struct bcw_index {
   // normalised list in pinned host memory, its device copy, and the event behind the last copy out of the pinned
   // buffer, which the next call waits for before it overwrites the buffer (the copy alone, not the stream)
   uint64_t* drop_h = nullptr;
-  uint64_t* drop_d = nullptr;
+  DevBuf<uint64_t> drop_d;
   hipEvent_t drop_ev = nullptr;
 };
 
@@ -1282,15 +1279,12 @@ int ix_room(bcw_index* x, uint64_t n, uint64_t arena_bytes) {
   }
   if (n > x->op_cap) {
     (void)hipStreamSynchronize(x->ctx->cur);
-    (void)hipFree(x->op_kref);
-    (void)hipFree(x->op_hash);
-    (void)hipFree(x->op_slot);
-    x->op_kref = x->op_hash = x->op_slot = nullptr;
+    x->op_kref.reset();
+    x->op_hash.reset();
+    x->op_slot.reset();
     x->op_cap = 0;
     const uint64_t c = std::max<uint64_t>(n, 1024);
-    if (hipMalloc(&x->op_kref, c * 8) != hipSuccess || hipMalloc(&x->op_hash, c * 8) != hipSuccess ||
-        hipMalloc(&x->op_slot, c * 8) != hipSuccess)
-      return BCW_E_NOMEM;
+    if (!x->op_kref.alloc(c * 8) || !x->op_hash.alloc(c * 8) || !x->op_slot.alloc(c * 8)) return BCW_E_NOMEM;
     x->op_cap = c;
   }
   x->slots_ub += n;
@@ -1299,14 +1293,7 @@ int ix_room(bcw_index* x, uint64_t n, uint64_t arena_bytes) {
 }
 
 int ix_stage(bcw_index* x, uint64_t bytes) {
-  if (bytes <= x->stage_cap) return BCW_OK;
-  (void)hipStreamSynchronize(x->ctx->cur);
-  (void)hipFree(x->stage);
-  x->stage = nullptr;
-  x->stage_cap = 0;
-  if (hipMalloc(&x->stage, bytes) != hipSuccess) return BCW_E_NOMEM;
-  x->stage_cap = bytes;
-  return BCW_OK;
+  return x->stage.reserve(bytes, x->ctx->cur) ? BCW_OK : BCW_E_NOMEM;
 }
 
 // The flat keys of a host call, key i = h_keys[h_key_off[i], h_key_off[i + 1]), n > 0: flat_keys_ok refuses offsets
@@ -1328,7 +1315,7 @@ int stage_flat_keys(bcw_index* x, uint64_t n, const uint8_t* h_keys, const uint6
   const uint64_t kb = h_key_off[n] - h_key_off[0], kbp = (kb + 15) & ~15ull;
   const int rc = ix_stage(x, kbp + 8 * (n + 1) + rest + 64);
   if (rc != BCW_OK) return rc;
-  uint8_t* d_keys = (uint8_t*)x->stage;
+  uint8_t* d_keys = (uint8_t*)x->stage.get();
   uint64_t* d_koff = (uint64_t*)(d_keys + kbp);
   hipStream_t st = x->ctx->cur;
   f->koff.resize(n + 1);
@@ -1356,12 +1343,12 @@ void ix_batch(bcw_index* x, const Src& s, uint64_t n, const bcw_decode_result* R
   const uint32_t grid = (uint32_t)((n + 255) / 256);
   (void)zero_group(x->cnt + C_NIN, st);
   if (!grid) return;
-  k_ix_keys<<<grid, 256, 0, st>>>(s, n, R, gen, x->cnt, x->op_kref, x->op_hash);
-  k_ix_claim<<<grid, 256, 0, st>>>(s, n, x->cnt, x->slots, x->cap - 1, x->arena, x->cnt, x->op_kref, x->op_hash,
-                                   x->op_slot, old_found, old_fid, old_size);
-  k_ix_seq<<<grid, 256, 0, st>>>(n, x->cnt, s.kind == SRC_FLAT, x->slots, x->op_slot, x->seq_base);
-  k_ix_commit<<<grid, 256, 0, st>>>(s, n, x->cnt, x->slots, x->arena, x->arena_cap, x->op_hash, x->op_slot);
-  k_ix_write<<<grid, 256, 0, st>>>(s, n, x->cnt, v, x->slots, x->op_slot, x->seq_base);
+  k_ix_keys<<<grid, 256, 0, st>>>(s, n, R, gen, x->cnt, x->op_kref.get(), x->op_hash.get());
+  k_ix_claim<<<grid, 256, 0, st>>>(s, n, x->cnt, x->slots, x->cap - 1, x->arena, x->cnt, x->op_kref.get(),
+                                   x->op_hash.get(), x->op_slot.get(), old_found, old_fid, old_size);
+  k_ix_seq<<<grid, 256, 0, st>>>(n, x->cnt, s.kind == SRC_FLAT, x->slots, x->op_slot.get(), x->seq_base);
+  k_ix_commit<<<grid, 256, 0, st>>>(s, n, x->cnt, x->slots, x->arena, x->arena_cap, x->op_hash.get(), x->op_slot.get());
+  k_ix_write<<<grid, 256, 0, st>>>(s, n, x->cnt, v, x->slots, x->op_slot.get(), x->seq_base);
   x->seq_base += n;
   ix_bound(x);
 }
@@ -1371,7 +1358,7 @@ Src table_src(bcw_ctx* c, const uint8_t* d_seg, const bcw_decode_params* p, cons
   s.kind = kind;
   s.seg = d_seg;
   s.seg_len = p->seg_len;
-  s.frags = c->s.frags;
+  s.frags = c->s.frags.get();
   s.t = *t;
   s.start_off = p->start_off;
   s.ns = p->ns_size;
@@ -1452,10 +1439,9 @@ int ix_usage_sync(bcw_index* x, bcw_fid_usage* h_rows, uint32_t cap, bcw_usage_r
   bcw_ctx* c = x->ctx;
   DeviceGuard dg(c->device);
   if (!dg.ok) return BCW_E_HIP;
-  void* mem = nullptr;
-  if (hipMalloc(&mem, sizeof(bcw_usage_result) + (uint64_t)cap * sizeof(bcw_fid_usage)) != hipSuccess)
-    return BCW_E_NOMEM;
-  bcw_usage_result* d_res = static_cast<bcw_usage_result*>(mem);
+  DevBuf<> mem;
+  if (!mem.alloc(sizeof(bcw_usage_result) + (uint64_t)cap * sizeof(bcw_fid_usage))) return BCW_E_NOMEM;
+  bcw_usage_result* d_res = static_cast<bcw_usage_result*>(mem.get());
   bcw_fid_usage* d_rows = cap ? reinterpret_cast<bcw_fid_usage*>(d_res + 1) : nullptr;
   int rc = async(d_rows, d_res);
   if (rc == BCW_OK &&
@@ -1469,8 +1455,7 @@ int ix_usage_sync(bcw_index* x, bcw_fid_usage* h_rows, uint32_t cap, bcw_usage_r
            hipSuccess ||
        hipStreamSynchronize(c->cur) != hipSuccess))
     rc = BCW_E_HIP;
-  (void)hipStreamSynchronize(c->cur);
-  (void)hipFree(mem);
+  (void)hipStreamSynchronize(c->cur);  // before mem goes
   return rc;
 }
 
@@ -1498,10 +1483,10 @@ int ix_put_batch(bcw_index* x, const PutIx& p) {
     ix_batch(x, s, p.n, nullptr, 0, v, p.found, p.free_fid, p.free_bytes);
     if (p.found) {
       const uint32_t grid = (uint32_t)((p.n + 255) / 256);
-      uint64_t* link = x->op_kref;  // free again once k_ix_claim has run
-      k_put_link<<<grid, 256, 0, st>>>(x->cnt, x->slots, x->op_slot, link);
-      k_put_stat<<<grid, 256, 0, st>>>(s, x->cnt, x->slots, x->op_slot, link, p.found, p.free_fid, p.free_bytes);
-      k_put_unlink<<<grid, 256, 0, st>>>(x->cnt, x->slots, x->op_slot);
+      uint64_t* link = x->op_kref.get();  // free again once k_ix_claim has run
+      k_put_link<<<grid, 256, 0, st>>>(x->cnt, x->slots, x->op_slot.get(), link);
+      k_put_stat<<<grid, 256, 0, st>>>(s, x->cnt, x->slots, x->op_slot.get(), link, p.found, p.free_fid, p.free_bytes);
+      k_put_unlink<<<grid, 256, 0, st>>>(x->cnt, x->slots, x->op_slot.get());
     }
   }
   if (p.idx_err) k_put_idx_err<<<1, 1, 0, st>>>(x->cnt, p.idx_err);
@@ -1522,8 +1507,8 @@ int ix_export(bcw_index* x, const uint64_t* h_fids, uint64_t n_fids, IxSink& sin
   // staging: fids | per-block entry counts | per-block key bytes (then their exclusive prefixes) | outputs
   int rc = ix_stage(x, fb + nblk * 16 + 64);
   if (rc != BCW_OK) return rc;
-  uint64_t* d_fids = (uint64_t*)x->stage;
-  uint64_t* blk_n = (uint64_t*)((uint8_t*)x->stage + fb);
+  uint64_t* d_fids = (uint64_t*)x->stage.get();
+  uint64_t* blk_n = (uint64_t*)((uint8_t*)x->stage.get() + fb);
   uint64_t* blk_b = blk_n + nblk;
   if (nf && hipMemcpyAsync(d_fids, fids.data(), 8 * (uint64_t)nf, hipMemcpyHostToDevice, st) != hipSuccess)
     return BCW_E_HIP;
@@ -1549,8 +1534,8 @@ int ix_export(bcw_index* x, const uint64_t* h_fids, uint64_t n_fids, IxSink& sin
   const uint64_t tbp = (tb + 15) & ~15ull;
   rc = ix_stage(x, fb + nblk * 16 + tbp + 8 * (tn + 1) + 24 * tn + 64);  // a regrow drops the contents
   if (rc != BCW_OK) return rc;
-  d_fids = (uint64_t*)x->stage;
-  uint64_t* pn = (uint64_t*)((uint8_t*)x->stage + fb);
+  d_fids = (uint64_t*)x->stage.get();
+  uint64_t* pn = (uint64_t*)((uint8_t*)x->stage.get() + fb);
   uint64_t* pb = pn + nblk;
   uint8_t* keys = (uint8_t*)(pb + nblk);
   uint64_t* koff = (uint64_t*)(keys + tbp);
@@ -1642,8 +1627,7 @@ int bcw_index_destroy(bcw_index* x) {
   if (!x) return BCW_E_INVAL;
   DeviceGuard dg(x->ctx->device);
   (void)hipStreamSynchronize(x->ctx->cur);
-  void* ptrs[] = {x->slots, x->arena, x->cnt, x->op_kref, x->op_hash, x->op_slot, x->stage, x->d_res,
-                  x->d_rule_tab, x->d_rule_cnt, x->drop_d};
+  void* ptrs[] = {x->slots, x->arena, x->cnt, x->d_res, x->d_rule_tab, x->d_rule_cnt};
   for (void* q : ptrs) (void)hipFree(q);
   if (x->drop_h) (void)hipHostFree(x->drop_h);
   if (x->drop_ev) (void)hipEventDestroy(x->drop_ev);
@@ -1999,15 +1983,12 @@ int bcw_index_drop_fids_async(bcw_index* x, int mode, const uint64_t* h_fids, ui
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ix_drop), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)bytes);
     (void)hipGetLastError();
-    if (hipMalloc(&x->drop_d, bytes) != hipSuccess) {
-      x->drop_d = nullptr;
-      return BCW_E_NOMEM;
-    }
+    if (!x->drop_d.alloc(bytes)) return BCW_E_NOMEM;
     if (hipHostMalloc(&x->drop_h, bytes, hipHostMallocDefault) != hipSuccess ||
         hipEventCreateWithFlags(&x->drop_ev, hipEventDisableTiming) != hipSuccess) {
       if (x->drop_h) (void)hipHostFree(x->drop_h);
-      (void)hipFree(x->drop_d);
-      x->drop_h = x->drop_d = nullptr;
+      x->drop_d.reset();
+      x->drop_h = nullptr;
       x->drop_ev = nullptr;
       return BCW_E_NOMEM;
     }
@@ -2016,7 +1997,8 @@ int bcw_index_drop_fids_async(bcw_index* x, int mode, const uint64_t* h_fids, ui
   }
   if (nf) {
     memcpy(x->drop_h, fids.data(), (size_t)nf * sizeof(uint64_t));
-    if (hipMemcpyAsync(x->drop_d, x->drop_h, (size_t)nf * sizeof(uint64_t), hipMemcpyHostToDevice, st) != hipSuccess)
+    if (hipMemcpyAsync(x->drop_d.get(), x->drop_h, (size_t)nf * sizeof(uint64_t), hipMemcpyHostToDevice, st) !=
+        hipSuccess)
       return BCW_E_HIP;
   }
   if (hipEventRecord(x->drop_ev, st) != hipSuccess) return BCW_E_HIP;
@@ -2024,7 +2006,7 @@ int bcw_index_drop_fids_async(bcw_index* x, int mode, const uint64_t* h_fids, ui
   rc = usage_begin(c, st, &scratch);
   if (rc != BCW_OK) return rc;
   rc = ix_usage_pass(x, K_IX_DROP, st, [&](uint32_t grid) {
-    k_ix_drop<<<grid, usage::kThreads, (size_t)nf * sizeof(uint64_t), st>>>(x->slots, x->cap, x->drop_d, nf, mode,
+    k_ix_drop<<<grid, usage::kThreads, (size_t)nf * sizeof(uint64_t), st>>>(x->slots, x->cap, x->drop_d.get(), nf, mode,
                                                                            scratch, x->cnt);
   });
   return rc != BCW_OK ? rc : usage_finish(c, st, d_rows, cap, d_res, 1);

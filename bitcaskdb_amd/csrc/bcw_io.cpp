@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "bcw.h"
-#include "bcw_internal.h"
+#include "bcw_host.h"
 
 namespace {
 

@@ -23,7 +23,7 @@
 
 #include "bcw_crc_dev.h"
 #include "bcw_frame.h"
-#include "bcw_internal.h"
+#include "bcw_host.h"
 
 namespace bcw {
 namespace put {
@@ -175,7 +175,7 @@ struct WArgs {
   const uint64_t* dpos;
   const uint8_t* lit;
   const uint32_t* hlen;
-  const uint32_t* wops;   // enc_ops (layout in bcw_internal.h)
+  const uint32_t* wops;   // enc_ops (layout in bcw_crc_consts.h)
   const uint32_t* initc;  // A_{8L}(0xFFFFFFFF)
 };
 
@@ -350,13 +350,6 @@ __global__ __launch_bounds__(kPT) void k_put_write(WArgs A) {
 
 }  // namespace put
 
-void put_scratch_free(PutScratch& s) {
-  (void)hipFree(s.lit);
-  (void)hipFree(s.hlen);
-  (void)hipFree(s.frags);
-  s = PutScratch{};
-}
-
 namespace {
 
 int put_scratch_reserve(bcw_ctx* c, uint64_t rows, uint64_t lit_bytes, uint64_t nfrags) {
@@ -365,10 +358,9 @@ int put_scratch_reserve(bcw_ctx* c, uint64_t rows, uint64_t lit_bytes, uint64_t 
   (void)hipStreamSynchronize(c->cur);
   const uint64_t r = std::max(rows, s.rows_cap), l = std::max(lit_bytes, s.lit_cap), f = std::max(nfrags, s.frag_cap);
   const int wr = s.write_resident;
-  put_scratch_free(s);
-  if (hipMalloc(&s.lit, l) != hipSuccess || hipMalloc(&s.hlen, r * 4) != hipSuccess ||
-      hipMalloc(&s.frags, f * sizeof(put::PFrag)) != hipSuccess) {
-    put_scratch_free(s);
+  s = PutScratch{};  // frees the three arrays
+  if (!s.lit.alloc(l) || !s.hlen.alloc(r * 4) || !s.frags.alloc(f * sizeof(put::PFrag))) {
+    s = PutScratch{};
     return BCW_E_NOMEM;
   }
   s.write_resident = wr;
@@ -475,26 +467,27 @@ int bcw_write_records_async(bcw_index* ix, const bcw_write_params* p, const bcw_
   enc_layout_reset(es, st);
   if (n) {
     pr.begin(K_PUT_PREP, st, ev);
-    put::k_put_prep<<<grid, 256, 0, st>>>(d, es.sz, ps.lit, ps.hlen, es.emisc);
+    put::k_put_prep<<<grid, 256, 0, st>>>(d, es.sz.get(), ps.lit.get(), ps.hlen.get(), es.emisc.get());
     pr.end(K_PUT_PREP, st, ev);
     pr.begin(K_PUT_LAYOUT, st, ev);
     if (enc_layout_run(es, n, p->wal_pos, st) != hipSuccess) return BCW_E_HIP;
     pr.end(K_PUT_LAYOUT, st, ev);
   }
   pr.begin(K_PUT_FRAGS, st, ev);
-  put::k_put_plan<<<1, 1, 0, st>>>(d, es.emisc, d_result);
-  if (n) put::k_put_frags<<<grid, 256, 0, st>>>(d, es.sz, es.dpos, es.emisc, static_cast<put::PFrag*>(ps.frags), fcap);
+  put::k_put_plan<<<1, 1, 0, st>>>(d, es.emisc.get(), d_result);
+  if (n) put::k_put_frags<<<grid, 256, 0, st>>>(d, es.sz.get(), es.dpos.get(), es.emisc.get(),
+                                           static_cast<put::PFrag*>(ps.frags.get()), fcap);
   pr.end(K_PUT_FRAGS, st, ev);
   if (n) {
     put::WArgs W{};
     W.d = d;
-    W.emisc = es.emisc;
-    W.frags = static_cast<const put::PFrag*>(ps.frags);
+    W.emisc = es.emisc.get();
+    W.frags = static_cast<const put::PFrag*>(ps.frags.get());
     W.fcap = fcap;
-    W.sz = es.sz;
-    W.dpos = es.dpos;
-    W.lit = ps.lit;
-    W.hlen = ps.hlen;
+    W.sz = es.sz.get();
+    W.dpos = es.dpos.get();
+    W.lit = ps.lit.get();
+    W.hlen = ps.hlen.get();
     W.wops = c->tabs.enc_ops;
     W.initc = c->tabs.initc;
     // a grid of resident workgroups: each wave walks the fragment list with the grid's stride, and the tables are
@@ -516,7 +509,7 @@ int bcw_write_records_async(bcw_index* ix, const bcw_write_params* p, const bcw_
   q.keys = b->keys;
   q.koff = b->key_off;
   q.keys_len = b->keys_len;
-  q.n_in = es.emisc + put::P_NIN;
+  q.n_in = es.emisc.get() + put::P_NIN;
   q.rec_off = o->rec_off;
   q.rec_size = o->rec_size;
   q.flags = b->flags;
@@ -560,51 +553,24 @@ int bcw_write_records(bcw_index* ix, const bcw_write_params* p, const bcw_write_
   DeviceGuard dg(c->device);
   if (!dg.ok) return BCW_E_HIP;
   const uint64_t eb = (any_etag && hb->etags) ? n * (uint64_t)p->etag_size : 0;
-  auto r16 = [](uint64_t v) { return (v + 15) & ~15ull; };
-  // keys | values | metas | etags | wal | three offset arrays, expire | rec_off, rec_size, free_fid, free_bytes |
-  // flags, found | result
-  const uint64_t bytes = r16(kb) + r16(vb) + r16(mb) + r16(eb) + r16(ho->wal_cap) + 3 * 8 * (n + 1) + 8 * n + 32 * n +
-                         r16(n) + r16(n) + sizeof(bcw_write_result) + 64;
-  void* mem = nullptr;
-  if (hipMalloc(&mem, bytes) != hipSuccess) return BCW_E_NOMEM;
-  uint8_t* m = (uint8_t*)mem;
+  DevBuf<> mem;
+  PutLayout L;
+  if (int rc = carve_alloc(mem, [&](Carver& cv) { L = carve_put(cv, kb, vb, mb, eb, ho->wal_cap, n, stat); })) return rc;
+  const bcw_write_out& d = L.out;
   bcw_write_batch db{};
-  bcw_write_out d{};
   db.n = n;
-  uint8_t* d_keys = m; m += r16(kb);
-  uint8_t* d_vals = m; m += r16(vb);
-  uint8_t* d_metas = m; m += r16(mb);
-  uint8_t* d_etags = m; m += r16(eb);
-  d.wal = m; m += r16(ho->wal_cap);
-  d.wal_cap = ho->wal_cap;
-  uint64_t* d_koff = (uint64_t*)m; m += 8 * (n + 1);
-  uint64_t* d_voff = (uint64_t*)m; m += 8 * (n + 1);
-  uint64_t* d_moff = (uint64_t*)m; m += 8 * (n + 1);
-  uint64_t* d_exp = (uint64_t*)m; m += 8 * n;
-  d.rec_off = (uint64_t*)m; m += 8 * n;
-  d.rec_size = (uint64_t*)m; m += 8 * n;
-  uint64_t* d_ffid = (uint64_t*)m; m += 8 * n;
-  uint64_t* d_fbytes = (uint64_t*)m; m += 8 * n;
-  uint8_t* d_flags = m; m += r16(n);
-  uint8_t* d_found = m; m += r16(n);
-  bcw_write_result* d_res = (bcw_write_result*)m;
-  if ((uint8_t*)(d_res + 1) > (uint8_t*)mem + bytes) {  // the carve-up above must stay inside the allocation
-    (void)hipFree(mem);
-    return BCW_E_INVAL;
-  }
-  if (stat) { d.found = d_found; d.free_fid = d_ffid; d.free_bytes = d_fbytes; }
-  db.keys = kb ? d_keys : nullptr;
-  db.key_off = d_koff;
+  db.keys = kb ? L.keys : nullptr;
+  db.key_off = L.offs;
   db.keys_len = kb;
-  db.vals = vb ? d_vals : nullptr;
-  db.val_off = d_voff;
+  db.vals = vb ? L.vals : nullptr;
+  db.val_off = L.offs + (n + 1);
   db.vals_len = vb;
-  db.metas = mb ? d_metas : nullptr;
-  db.meta_off = d_moff;
+  db.metas = mb ? L.metas : nullptr;
+  db.meta_off = L.offs + 2 * (n + 1);
   db.metas_len = mb;
-  db.etags = eb ? d_etags : nullptr;
-  db.expire = d_exp;
-  db.flags = d_flags;
+  db.etags = eb ? L.etags : nullptr;
+  db.expire = L.expire;
+  db.flags = L.flags;
   hipStream_t st = c->cur;
   std::vector<uint64_t> off(3 * (n + 1));
   for (uint64_t i = 0; n && i <= n; ++i) {
@@ -620,24 +586,23 @@ int bcw_write_records(bcw_index* ix, const bcw_write_params* p, const bcw_write_
   };
   bool ok = true;
   if (n)
-    ok = up(d_keys, kb ? hb->keys + hb->key_off[0] : nullptr, kb) &&
-         up(d_vals, vb ? hb->vals + hb->val_off[0] : nullptr, vb) &&
-         up(d_metas, mb ? hb->metas + hb->meta_off[0] : nullptr, mb) && up(d_etags, hb->etags, eb) &&
-         up(d_koff, off.data(), 3 * 8 * (n + 1)) && up(d_exp, hb->expire, 8 * n) && up(d_flags, hb->flags, n);
-  int rc = ok ? bcw_write_records_async(ix, p, &db, &d, d_res) : BCW_E_HIP;
+    ok = up(L.keys, kb ? hb->keys + hb->key_off[0] : nullptr, kb) &&
+         up(L.vals, vb ? hb->vals + hb->val_off[0] : nullptr, vb) &&
+         up(L.metas, mb ? hb->metas + hb->meta_off[0] : nullptr, mb) && up(L.etags, hb->etags, eb) &&
+         up(L.offs, off.data(), 3 * 8 * (n + 1)) && up(L.expire, hb->expire, 8 * n) && up(L.flags, hb->flags, n);
+  int rc = ok ? bcw_write_records_async(ix, p, &db, &d, L.res) : BCW_E_HIP;
   if (rc == BCW_OK) {
-    ok = down(h_result, d_res, sizeof(bcw_write_result)) && hipStreamSynchronize(st) == hipSuccess;
+    ok = down(h_result, L.res, sizeof(bcw_write_result)) && hipStreamSynchronize(st) == hipSuccess;
     rc = !ok ? BCW_E_HIP : h_result->fits ? BCW_OK : BCW_E_CAPACITY;
   }
   if (rc == BCW_OK && h_result->n_written) {
     ok = down(ho->wal, d.wal, h_result->wal_need) && down(ho->rec_off, d.rec_off, 8 * n) &&
          down(ho->rec_size, d.rec_size, 8 * n);
     if (ok && stat)
-      ok = down(ho->found, d_found, n) && down(ho->free_fid, d_ffid, 8 * n) && down(ho->free_bytes, d_fbytes, 8 * n);
+      ok = down(ho->found, d.found, n) && down(ho->free_fid, d.free_fid, 8 * n) && down(ho->free_bytes, d.free_bytes, 8 * n);
     if (!ok) rc = BCW_E_HIP;
   }
-  if (hipStreamSynchronize(st) != hipSuccess && rc == BCW_OK) rc = BCW_E_HIP;
-  (void)hipFree(mem);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == BCW_OK) rc = BCW_E_HIP;  // before mem goes
   return rc;
 }
 

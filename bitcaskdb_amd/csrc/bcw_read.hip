@@ -16,7 +16,7 @@
 #include <cstring>
 #include <vector>
 
-#include "bcw_internal.h"
+#include "bcw_host.h"
 #include "bcw_read_body.h"
 
 namespace bcw {
@@ -87,10 +87,7 @@ int bcw_read_records_async(bcw_ctx* c, const uint8_t* d_seg, const bcw_read_para
                            const uint64_t* d_off, const uint64_t* d_size, const uint64_t* d_pay_off, uint8_t* d_payload,
                            uint8_t* d_rd_status, const bcw_record_table* d_table) {
   if (!c || !p || (n && (!d_seg || !d_off || !d_size || !d_pay_off || !d_payload || !d_rd_status))) return BCW_E_INVAL;
-  if (d_table && d_table->status && (!d_table->foff || !d_table->size || !d_table->expire || !d_table->key_len ||
-                                     !d_table->val_len || !d_table->meta_len || !d_table->hdr_size ||
-                                     !d_table->flags || !d_table->etag_off))
-    return BCW_E_INVAL;
+  if (d_table && !read_table_ok(*d_table)) return BCW_E_INVAL;
   DeviceGuard dg(c->device);
   if (!dg.ok) return BCW_E_HIP;
   rd::ReadArgs A{};
@@ -117,55 +114,21 @@ int bcw_read_records(bcw_ctx* c, const uint8_t* h_seg, const bcw_read_params* p,
   if (!dg.ok) return BCW_E_HIP;
   std::vector<uint64_t> pay(n + 1, 0);
   for (uint64_t i = 0; i < n; ++i) pay[i + 1] = pay[i] + h_size[i];
-  const uint64_t pb = (pay[n] + 15) & ~15ull, sb = (p->seg_len + 15) & ~15ull;
   const bool tab = h_table && h_table->status;
-  const uint64_t tb = tab ? n * 64 : 0;
-  void* mem = nullptr;
-  if (hipMalloc(&mem, sb + pb + 8 * (3 * n + 1) + n + tb + 64) != hipSuccess) return BCW_E_NOMEM;
-  uint8_t* m = (uint8_t*)mem;
-  uint8_t* d_seg = m; m += sb;
-  uint8_t* d_pay = m; m += pb;
-  uint64_t* d_off = (uint64_t*)m; m += 8 * n;
-  uint64_t* d_size = (uint64_t*)m; m += 8 * n;
-  uint64_t* d_pay_off = (uint64_t*)m; m += 8 * (n + 1);
-  bcw_record_table dt{};
-  if (tab) {
-    dt.capacity = n;
-    dt.foff = (uint64_t*)m; m += 8 * n;
-    dt.size = (uint64_t*)m; m += 8 * n;
-    dt.expire = (uint64_t*)m; m += 8 * n;
-    dt.key_len = (uint32_t*)m; m += 4 * n;
-    dt.val_len = (uint32_t*)m; m += 4 * n;
-    dt.meta_len = (uint32_t*)m; m += 4 * n;
-    dt.first_frag = (uint32_t*)m; m += 4 * n;
-    dt.emit_frag = (uint32_t*)m; m += 4 * n;
-    dt.hdr_size = m; m += n;
-    dt.flags = m; m += n;
-    dt.etag_off = m; m += n;
-    dt.status = m; m += n;
-  }
-  uint8_t* d_st = m;
+  DevBuf<> mem;
+  ReadLayout d;
+  if (const int rc = carve_alloc(mem, [&](Carver& cv) { d = carve_read(cv, p->seg_len, pay[n], n, tab); })) return rc;
   hipStream_t st = c->cur;
-  bool ok = (p->seg_len == 0 || hipMemcpyAsync(d_seg, h_seg, p->seg_len, hipMemcpyHostToDevice, st) == hipSuccess) &&
-            hipMemcpyAsync(d_off, h_off, 8 * n, hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(d_size, h_size, 8 * n, hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(d_pay_off, pay.data(), 8 * (n + 1), hipMemcpyHostToDevice, st) == hipSuccess;
-  ok = ok && bcw_read_records_async(c, d_seg, p, n, d_off, d_size, d_pay_off, d_pay, d_st, tab ? &dt : nullptr) == BCW_OK;
-  ok = ok && (pay[n] == 0 || hipMemcpyAsync(h_payload, d_pay, pay[n], hipMemcpyDeviceToHost, st) == hipSuccess) &&
-       hipMemcpyAsync(h_rd_status, d_st, n, hipMemcpyDeviceToHost, st) == hipSuccess;
-  if (ok && tab) {
-    const uint64_t k = std::min(n, h_table->capacity);
-    auto cp = [&](void* dst, const void* src, size_t esz) {
-      return !dst || hipMemcpyAsync(dst, src, k * esz, hipMemcpyDeviceToHost, st) == hipSuccess;
-    };
-    ok = cp(h_table->foff, dt.foff, 8) && cp(h_table->size, dt.size, 8) && cp(h_table->expire, dt.expire, 8) &&
-         cp(h_table->key_len, dt.key_len, 4) && cp(h_table->val_len, dt.val_len, 4) &&
-         cp(h_table->meta_len, dt.meta_len, 4) && cp(h_table->first_frag, dt.first_frag, 4) &&
-         cp(h_table->emit_frag, dt.emit_frag, 4) && cp(h_table->hdr_size, dt.hdr_size, 1) &&
-         cp(h_table->flags, dt.flags, 1) && cp(h_table->etag_off, dt.etag_off, 1) && cp(h_table->status, dt.status, 1);
-  }
-  ok = ok && hipStreamSynchronize(st) == hipSuccess;
-  (void)hipFree(mem);
+  bool ok = (p->seg_len == 0 || hipMemcpyAsync(d.seg, h_seg, p->seg_len, hipMemcpyHostToDevice, st) == hipSuccess) &&
+            hipMemcpyAsync(d.off, h_off, 8 * n, hipMemcpyHostToDevice, st) == hipSuccess &&
+            hipMemcpyAsync(d.size, h_size, 8 * n, hipMemcpyHostToDevice, st) == hipSuccess &&
+            hipMemcpyAsync(d.pay_off, pay.data(), 8 * (n + 1), hipMemcpyHostToDevice, st) == hipSuccess;
+  ok = ok && bcw_read_records_async(c, d.seg, p, n, d.off, d.size, d.pay_off, d.payload, d.rd_status,
+                                    tab ? &d.tab : nullptr) == BCW_OK;
+  ok = ok && (pay[n] == 0 || hipMemcpyAsync(h_payload, d.payload, pay[n], hipMemcpyDeviceToHost, st) == hipSuccess) &&
+       hipMemcpyAsync(h_rd_status, d.rd_status, n, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (ok && tab) ok = table_copy_down(*h_table, d.tab, std::min(n, h_table->capacity), st);
+  ok = ok && hipStreamSynchronize(st) == hipSuccess;  // any failure of the async half is reported as BCW_E_HIP
   return ok ? BCW_OK : BCW_E_HIP;
 }
 

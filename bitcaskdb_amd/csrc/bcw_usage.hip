@@ -9,7 +9,7 @@
 
 #include <algorithm>
 
-#include "bcw_internal.h"
+#include "bcw_host.h"
 #include "bcw_usage.h"
 
 namespace bcw {
@@ -129,12 +129,9 @@ __global__ __launch_bounds__(kFinalThreads) void k_usage_final(uint64_t* __restr
 }  // namespace usage
 
 int usage_begin(bcw_ctx* c, hipStream_t st, uint64_t** scratch) {
-  if (!c->usage && hipMalloc(&c->usage, usage::kScratchWords * sizeof(uint64_t)) != hipSuccess) {
-    c->usage = nullptr;
-    return BCW_E_NOMEM;
-  }
-  if (hipMemsetAsync(c->usage, 0, usage::kScratchWords * sizeof(uint64_t), st) != hipSuccess) return BCW_E_HIP;
-  *scratch = c->usage;
+  if (!c->usage && !c->usage.alloc(usage::kScratchWords * sizeof(uint64_t))) return BCW_E_NOMEM;
+  if (hipMemsetAsync(c->usage.get(), 0, usage::kScratchWords * sizeof(uint64_t), st) != hipSuccess) return BCW_E_HIP;
+  *scratch = c->usage.get();
   return BCW_OK;
 }
 
@@ -142,7 +139,7 @@ int usage_finish(bcw_ctx* c, hipStream_t st, bcw_fid_usage* d_rows, uint32_t cap
                  int index_pass) {
   hipEvent_t ev = nullptr;
   c->prof.begin(K_USAGE_FINAL, st, ev);
-  usage::k_usage_final<<<1, usage::kFinalThreads, 0, st>>>(c->usage, d_rows, cap, d_res, index_pass);
+  usage::k_usage_final<<<1, usage::kFinalThreads, 0, st>>>(c->usage.get(), d_rows, cap, d_res, index_pass);
   c->prof.end(K_USAGE_FINAL, st, ev);
   return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
 }

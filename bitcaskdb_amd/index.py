@@ -337,11 +337,12 @@ class Index:
 
     # ---- batched Get by key (DBImpl.Get, db_impl.go:567-587) ----
     def get_batch(self, walset: "WalSet", keys, verify: bool = False, ns_size: int = 20, etag_size: int = 20,
-                  payload_cap: int | None = None, fill: int = 0) -> "GetBatch":
+                  payload_cap: int | None = None, fill: int = 0, table: bool = True) -> "GetBatch":
         """bcw_get_records of merged keys against the resident WALs of `walset`: the raw columns (GetBatch). With
         payload_cap None the call is retried once with the size the first one reports; with a given payload_cap it
         is made once, and a payload that does not fit comes back with rc E_CAPACITY and fits == 0 (the payload
-        buffer, pre-filled with `fill`, is then untouched)."""
+        buffer, pre-filled with `fill`, is then untouched). table False: no record table is asked for (its columns
+        come back zero)."""
         n = len(keys)
         flat, koff = _pack(keys)
         cap = payload_cap if payload_cap is not None else max(1 << 16, 1024 * n)
@@ -354,7 +355,7 @@ class Index:
             cols = {name: np.zeros(m, dtype=dt) for name, dt in L.TABLE_COLUMNS}
             tab = L.RecordTable(n, *[cols[name].ctypes.data_as(getattr(L, "u8p" if dt == "u1" else
                                                                        ("u32p" if dt == "u4" else "u64p")))
-                                     for name, dt in L.TABLE_COLUMNS])
+                                     for name, dt in L.TABLE_COLUMNS]) if table else L.RecordTable()
             out = L.GetOut(gst.ctypes.data_as(L.u8p), rst.ctypes.data_as(L.u8p), fid.ctypes.data_as(L.u64p),
                            off.ctypes.data_as(L.u64p), size.ctypes.data_as(L.u64p), pay_off.ctypes.data_as(L.u64p),
                            pay.ctypes.data_as(L.u8p), cap, tab)

@@ -190,8 +190,10 @@ class Context:
         return res, bytes(wal[:int(res.wal_need)]), bytes(hint[:int(res.hint_need)]), offs[:int(res.n_in)].copy()
 
     # synchronous batched point reads (Wal.ReadRecord + WalParseRecord + RecordFromBytes per request)
-    def read_records(self, seg, offsets, sizes, base_time: int, ns_size: int, etag_size: int, verify: bool = True):
-        """Returns (payload bytes per request, rd_status per request, record table dict)."""
+    def read_records(self, seg, offsets, sizes, base_time: int, ns_size: int, etag_size: int, verify: bool = True,
+                     table: bool = True):
+        """Returns (payload bytes per request, rd_status per request, record table dict). table False: no record
+        table is asked for (its columns come back zero)."""
         seg = np.ascontiguousarray(np.frombuffer(seg, dtype=np.uint8) if not isinstance(seg, np.ndarray) else seg,
                                    dtype=np.uint8)
         offs = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -205,10 +207,11 @@ class Context:
         cols = {name: np.zeros(max(n, 1), dtype=dt) for name, dt in L.TABLE_COLUMNS}
         tab = L.RecordTable(n, *[cols[name].ctypes.data_as(getattr(L, "u8p" if dt == "u1" else
                                                                    ("u32p" if dt == "u4" else "u64p")))
-                                 for name, dt in L.TABLE_COLUMNS])
+                                 for name, dt in L.TABLE_COLUMNS]) if table else None
         rc = L.lib.bcw_read_records(self._h, seg.ctypes.data_as(C.c_void_p) if seg.size else None, C.byref(p), n,
                                     offs.ctypes.data_as(L.u64p), sizes.ctypes.data_as(L.u64p),
-                                    pay.ctypes.data_as(C.c_void_p), st.ctypes.data_as(L.u8p), C.byref(tab))
+                                    pay.ctypes.data_as(C.c_void_p), st.ctypes.data_as(L.u8p),
+                                    C.byref(tab) if table else None)
         if rc != 0:
             raise RuntimeError(f"bcw_read_records: {L.lib.bcw_strerror(rc).decode()}")
         ends = np.concatenate([[0], np.cumsum(sizes, dtype=np.uint64)]) if n else np.zeros(1, np.uint64)

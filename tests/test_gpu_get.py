@@ -237,6 +237,29 @@ def test_get_capacity(ctx, db):
     check(b, exp)
     b = db.ix.get_batch(db.ws, keys, False, NS, ETAG)  # the retry inside get_batch
     assert b.rc == 0 and int(b.result.payload_need) == need
+    # the sync call's device layout on both sides of a lookup workgroup (256 keys), with and without the optional
+    # table, and a payload buffer too small at each
+    first = next(i for i, e in enumerate(exp) if e[0] == L.GET_OK)  # the batch of one key has a payload
+    many = (db.query[first:] + db.query[:first])[:257]
+    assert len(many) == 257
+    for n in (1, 256, 257):
+        exp_n = expected(db, many[:n], False)
+        need_n = sum(e[5] for e in exp_n)
+        assert need_n > 16
+        with_tab = db.ix.get_batch(db.ws, [NSB + k for k in many[:n]], False, NS, ETAG)
+        check(with_tab, exp_n)
+        bare = db.ix.get_batch(db.ws, [NSB + k for k in many[:n]], False, NS, ETAG, table=False)
+        assert bare.rc == 0 and all(not col.any() for col in bare.table.values())
+        for c in ("get_status", "rd_status", "fid", "off", "size", "pay_off"):
+            np.testing.assert_array_equal(getattr(bare, c), getattr(with_tab, c), err_msg=c)
+        assert bare.payload[:need_n].tobytes() == with_tab.payload[:need_n].tobytes()
+        for f in ("n_found", "n_ok", "payload_need", "fits"):
+            assert getattr(bare.result, f) == getattr(with_tab.result, f), f
+        short = db.ix.get_batch(db.ws, [NSB + k for k in many[:n]], False, NS, ETAG, payload_cap=need_n - 1, fill=0xAB,
+                                table=False)
+        assert short.rc == L.E_CAPACITY and short.result.fits == 0 and int(short.result.payload_need) == need_n
+        assert (short.payload == 0xAB).all()
+        np.testing.assert_array_equal(short.pay_off, with_tab.pay_off)
 
 
 def test_get_leaves_index_untouched(ctx, db):

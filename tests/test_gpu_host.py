@@ -267,3 +267,52 @@ def test_two_contexts_two_threads():
     for t in th:
         t.join()
     assert not errors, errors
+
+
+def test_sync_staging_capacity_and_growth():
+    """the synchronous entry points' staging on a fresh context: a context destroyed with nothing run on it; a host
+    table of 2 rows for 3 records (BCW_E_CAPACITY, the first 2 rows delivered, nothing past them); a fragment table
+    shorter than the decode's; then a larger source, which grows every staging buffer and scratch of the context,
+    decoded and re-encoded as the oracle does, and the small one again in the buffers that grew."""
+    from bitcaskdb_amd import Context
+    Context(0).close()
+    c = Context(0)
+    try:
+        small, _ = cases.wal_of([cases.rec(i, vlen=40000 if i == 1 else 50) for i in range(3)])
+        ref = oracle_records(small)
+        assert len(ref.recs) == 3 and len(ref.frags) == 4
+        seg = np.frombuffer(small, dtype=np.uint8)
+        p = L.DecodeParams(len(small), BASE, 40, 20, 20, L.MODE_RECORD)
+        ptr = {"u1": L.u8p, "u4": L.u32p, "u8": L.u64p}
+        cols = {name: np.full(3, 0xEE, dtype=dt) for name, dt in L.TABLE_COLUMNS}
+        tab = L.RecordTable(2, *[cols[name].ctypes.data_as(ptr[dt]) for name, dt in L.TABLE_COLUMNS])
+        res = L.DecodeResult()
+        rc = L.lib.bcw_decode_segment(c.handle, seg.ctypes.data_as(C.c_void_p), C.byref(p), C.byref(tab), C.byref(res))
+        assert rc == L.E_CAPACITY and res.n_records == 3 and res.err_class == 0
+        for name, dt in L.TABLE_COLUMNS:
+            if name not in ("aux0", "aux1"):
+                want = ref.recs[name][:2].astype(np.uint64) & (0xFFFFFFFF if dt == "u4" else 0xFFFFFFFFFFFFFFFF)
+                np.testing.assert_array_equal(cols[name][:2].astype(np.uint64), want, err_msg=name)
+            assert cols[name][2] == np.full(1, 0xEE, dtype=dt)[0], name  # the row past the capacity is the caller's
+        # a fragment table of 2 entries for 4 fragments: the total, and the first 2
+        fc = {name: np.full(3, 0xEE, dtype=dt) for name, dt in L.FRAG_COLUMNS}
+        ft = L.FragTable(2, fc["data_off"].ctypes.data_as(L.u64p), fc["len"].ctypes.data_as(L.u32p),
+                         fc["stored_crc"].ctypes.data_as(L.u32p), fc["type"].ctypes.data_as(L.u8p),
+                         fc["crc_ok"].ctypes.data_as(L.u8p))
+        total = C.c_uint64(0)
+        assert L.lib.bcw_decode_fragments(c.handle, C.byref(ft), C.byref(total)) == 0 and total.value == 4
+        for name, dt in L.FRAG_COLUMNS:
+            np.testing.assert_array_equal(fc[name][:2], ref.frags[name][:2].astype(fc[name].dtype), err_msg=name)
+            assert fc[name][2] == np.full(1, 0xEE, dtype=dt)[0], name
+        # growth: the small source, a larger one (more blocks, rows and output bytes), the small one again
+        large, _ = cases.wal_of([cases.rec(i, vlen=3000 + i) for i in range(400)])
+        for data in (small, large, small):
+            rd, rh = O.Writer(BASE, BASE), O.Writer(BASE, BASE)
+            n = len(oracle_records(data).recs)
+            ec, _, nin, roffs = O.compact_append(rd, rh, 7, data, 40, BASE, BASE, 20, 20, np.ones(n, np.uint8))
+            r, wal, hint, offs = c.encode(data, L.ENC_COMPACT, 40, BASE, 7, 40, 40, 20, 20, np.ones(n, np.uint8))
+            assert ec == 0 and r.err_class == 0 and r.n_written == n == nin
+            assert wal == rd.data()[40:] and hint == rh.data()[40:]
+            np.testing.assert_array_equal(offs, roffs[:nin])
+    finally:
+        c.close()

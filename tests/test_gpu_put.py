@@ -109,8 +109,10 @@ class Out:
     pass
 
 
-def write_sync(ix: Index, batch: WriteBatch, pos: int, cap: int | None = None, ns_size=NS, etag_size=ETAG, fid=FID):
-    """bcw_write_records with every output pre-filled (0xA5 bytes, sentinel words)"""
+def write_sync(ix: Index, batch: WriteBatch, pos: int, cap: int | None = None, ns_size=NS, etag_size=ETAG, fid=FID,
+               stat: bool = True):
+    """bcw_write_records with every output pre-filled (0xA5 bytes, sentinel words); stat False: without the WriteStat
+    columns (found, free_fid, free_bytes)"""
     keys, koff, vals, voff, metas, moff, etags, expire, flags = arrs = batch.arrays(etag_size)
     n = batch.size()
     if cap is None:
@@ -123,7 +125,8 @@ def write_sync(ix: Index, batch: WriteBatch, pos: int, cap: int | None = None, n
     ba = L.WriteBatchArrays(n, _vp(keys), _vp(koff), keys.size, _vp(vals), _vp(voff), vals.size, _vp(metas), _vp(moff),
                             metas.size, _vp(etags), _vp(expire), _vp(flags))
     p = L.WriteParams(fid, BASE, pos, ns_size, etag_size)
-    out = L.WriteOut(_vp(o.wal), cap, _vp(o.rec_off), _vp(o.rec_size), _vp(o.found), _vp(o.ffid), _vp(o.fbytes))
+    out = L.WriteOut(_vp(o.wal), cap, _vp(o.rec_off), _vp(o.rec_size),
+                     *((_vp(o.found), _vp(o.ffid), _vp(o.fbytes)) if stat else (None, None, None)))
     o.res = L.WriteResult()
     o.rc = L.lib.bcw_write_records(ix.handle, C.byref(p), C.byref(ba), C.byref(out), C.byref(o.res))
     o.keep = arrs
@@ -381,6 +384,15 @@ def test_async_unaligned_inputs_equal_sync(ctx):
     ix_s, ix_a = Index(ctx, keys=1 << 12), Index(ctx, keys=1 << 12)
     s = write_sync(ix_s, b.batch, pos)
     assert_written(s, b)
+    # the sync call without the WriteStat columns: the same bytes, offsets and index, the three columns untouched
+    ix_n = Index(ctx, keys=1 << 12)
+    bare = write_sync(ix_n, b.batch, pos, stat=False)
+    assert_written(bare, b)
+    assert (bare.found == FILL).all() and (bare.ffid == SENT).all() and (bare.fbytes == SENT).all()
+    for f, _ in L.WriteResult._fields_:
+        assert getattr(bare.res, f) == getattr(s.res, f), f
+    assert_index(ix_n, oracle_index(b), b.ops)
+    ix_n.close()
     keys, koff, vals, voff, metas, moff, etags, expire, flags = b.batch.arrays(ETAG)
     d_keys = D.DevBuf(1 + keys.size).upload(keys, 1)
     d_vals = D.DevBuf(7 + vals.size).upload(vals, 7)  # the values end exactly at the allocation's end
@@ -421,6 +433,8 @@ def test_empty_batch(ix):
         o = write_sync(ix, WriteBatch(), pos)
         assert o.rc == 0 and o.res.wal_end == pos and o.res.wal_need == 0 and o.res.n_written == 0
         assert o.res.fits == 1 and o.res.err_class == 0 and (o.wal == FILL).all()
+        o = write_sync(ix, WriteBatch(), pos, stat=False)
+        assert o.rc == 0 and o.res.wal_end == pos and o.res.wal_need == 0 and o.res.n_written == 0 and o.res.fits == 1
 
 
 @pytest.mark.parametrize("ns_size,etag_size", [(0, 0), (8, 16)])

@@ -53,6 +53,12 @@ def test_read_records_payloads(ctx):
     assert (st == 0).all()
     got = W.read_records(W.load_wal(data), offs, sizes)
     assert all(isinstance(x, W.Record) for x in got)
+    # without the optional table (another device layout): the same payloads and statuses, no row
+    ref = ctx.read_records(data, offs, sizes, BASE, 20, 20)
+    for n in (1, len(offs)):
+        pays, st2, tab = ctx.read_records(data, offs[:n], sizes[:n], BASE, 20, 20, table=False)
+        assert pays == ref[0][:n] and (st2 == ref[1][:n]).all()
+        assert all(not col.any() for col in tab.values())
 
 
 def test_read_error_branches(ctx):

@@ -206,13 +206,13 @@ int main(int argc, char** argv) {
       float ms = 0;
       CK(hipEventElapsedTime(&ms, a, b));
       uint64_t mc[16];
-      CK(hipMemcpy(mc, s.misc, sizeof mc, hipMemcpyDeviceToHost));
+      CK(hipMemcpy(mc, s.misc.get(), sizeof mc, hipMemcpyDeviceToHost));
       printf("timeline: pipeline %.1f us; k_crc WG0 start -> finalize %.1f us\n", ms * 1e3,
              (mc[M_T_FIN] - mc[M_T_CRC0]) / 100.0);
     }
   }
   const uint64_t nblocks = (n - 40 + kBlock - 1) / kBlock;
-  const EmitArgs ea{d, n, p, s.frags, s.fbase, s.rbase, s.bsum, t, s.misc, 0u, nullptr};
+  const EmitArgs ea{d, n, p, s.frags.get(), s.fbase.get(), s.rbase.get(), s.bsum.get(), t, s.misc.get(), 0u, nullptr};
   EmitArgs ea_off = ea;
   ea_off.kb_flags = 1u;  // the product kernel with its emission skipped at run time
   EmitArgs ea_st = ea;   // ... with per-wave stamps of its CRC end, emission end and items
@@ -327,10 +327,10 @@ int main(int argc, char** argv) {
     EmitArgs a = a0;
     if (kb_clock && !a.kb_stamps) a.kb_stamps = seq_stamps ? seq_stamps : clk_st;
     if (run_reps == 0) {
-      kern<<<grid, kCrcThreads, 0, st>>>(d, n, 40, nblocks, s.fbase, s.fok, s.srec, s.frag_cap, ctx->tabs, a, 0u, 0ull, dres, s.misc, 0ull, nblocks, grid, s.wstart, s.xbal);
+      kern<<<grid, kCrcThreads, 0, st>>>(d, n, 40, nblocks, s.fbase.get(), s.fok.get(), s.srec.get(), s.frag_cap, ctx->tabs, a, 0u, 0ull, dres, s.misc.get(), 0ull, nblocks, grid, s.wstart.get(), s.xbal.get());
       return 0.0f;
     }
-    const float ms = timeit([&] { kern<<<grid, kCrcThreads, 0, st>>>(d, n, 40, nblocks, s.fbase, s.fok, s.srec, s.frag_cap, ctx->tabs, a, 0u, 0ull, dres, s.misc, 0ull, nblocks, grid, s.wstart, s.xbal); },
+    const float ms = timeit([&] { kern<<<grid, kCrcThreads, 0, st>>>(d, n, 40, nblocks, s.fbase.get(), s.fok.get(), s.srec.get(), s.frag_cap, ctx->tabs, a, 0u, 0ull, dres, s.misc.get(), 0ull, nblocks, grid, s.wstart.get(), s.xbal.get()); },
                   reps, st);
     if (kb_clock && a.kb_stamps == clk_st) last_mhz = clock_of(clk_st, grid * kCrcWaves);
     return ms;
@@ -359,10 +359,10 @@ int main(int argc, char** argv) {
     constexpr int WV = decltype(wv_c)::value;
     auto crun = [&](auto kern) {
       return timeit([&] {
-        kern<<<(uint32_t)((nblocks + 63) / 64), WV * 64, 0, st>>>(d, n, 40, nblocks, s.fbase, s.rbase, s.bsum, s.frags,
-                                                              s.srec, s.frag_cap, s.lb, s.lbe, s.misc, s.epoch,
-                                                              ctx->tabs.initc, s.chase_direct, 0ull, s.wstart,
-                                                              (uint32_t)cus * kCrcWaves, s.xbal, s.xbal_on);
+        kern<<<(uint32_t)((nblocks + 63) / 64), WV * 64, 0, st>>>(d, n, 40, nblocks, s.fbase.get(), s.rbase.get(), s.bsum.get(), s.frags.get(),
+                                                              s.srec.get(), s.frag_cap, s.lb.get(), s.lbe.get(), s.misc.get(), s.epoch,
+                                                              ctx->tabs.initc, s.chase_direct, 0ull, s.wstart.get(),
+                                                              (uint32_t)cus * kCrcWaves, s.xbal.get(), s.xbal_on);
         ++s.epoch;
       }, reps, st);
     };
@@ -381,9 +381,9 @@ int main(int argc, char** argv) {
       uint64_t* stp;
       CK(hipMalloc(&stp, nwg * 32));
       for (int rep = 0; rep < 3; ++rep) {
-        k_chase<32, WV><<<(uint32_t)nwg, WV * 64, 0, st>>>(d, n, 40, nblocks, s.fbase, s.rbase, s.bsum, s.frags, s.srec, s.frag_cap,
-                                                  s.lb, stp, s.misc, s.epoch, ctx->tabs.initc, s.chase_direct, 0ull,
-                                                  s.wstart, (uint32_t)cus * kCrcWaves, s.xbal, s.xbal_on);
+        k_chase<32, WV><<<(uint32_t)nwg, WV * 64, 0, st>>>(d, n, 40, nblocks, s.fbase.get(), s.rbase.get(), s.bsum.get(), s.frags.get(), s.srec.get(), s.frag_cap,
+                                                  s.lb.get(), stp, s.misc.get(), s.epoch, ctx->tabs.initc, s.chase_direct, 0ull,
+                                                  s.wstart.get(), (uint32_t)cus * kCrcWaves, s.xbal.get(), s.xbal_on);
         ++s.epoch;
         CK(hipStreamSynchronize(st));
       }
@@ -409,10 +409,10 @@ int main(int argc, char** argv) {
       printf("\n");
       CK(hipFree(stp));
     }
-    CK(hipMemset(&s.misc[7], 0, 24));
+    CK(hipMemset(&s.misc.get()[7], 0, 24));
     crun(k_chase<16, WV>);
     uint64_t m3[3];
-    CK(hipMemcpy(m3, &s.misc[7], 24, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(m3, &s.misc.get()[7], 24, hipMemcpyDeviceToHost));
     const double wl = (double)((nblocks + 63) / 64) * (reps + 1);
     printf("  k_chase phase cycles per workgroup (s_memtime): chase %.0f  sum %.0f  writes %.0f\n", m3[0] / wl,
            m3[1] / wl, m3[2] / wl);
@@ -494,7 +494,7 @@ int main(int argc, char** argv) {
       }
     std::sort(ton.begin(), ton.end()); std::sort(toff.begin(), toff.end());
     XBal xb;
-    CK(hipMemcpy(&xb, s.xbal, sizeof xb, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(&xb, s.xbal.get(), sizeof xb, hipMemcpyDeviceToHost));
     printf("xbal pipeline on: min %.4f median %.4f max %.4f ms | off: min %.4f median %.4f max %.4f ms\n", ton[0], ton[3],
            ton[6], toff[0], toff[3], toff[6]);
     printf("xbal weights:");
@@ -584,16 +584,16 @@ int main(int argc, char** argv) {
   printf("k_crc full      %.4f ms  %.1f GB/s\n", a0, n / (a0 * 1e-3) / 1e9);
   printf("k_crc fast chain only (no emission) %.4f  no emission %.4f  emission only %.4f ms\n", a1, a8, a9);
   const float as = timeit([&] {
-    hipMemsetAsync(&s.misc[M_DONE_CRC], 0, 8, st);  // the last workgroup finalizes
-    k_crc<0><<<cus, kCrcThreads, 0, st>>>(d, n, 40, nblocks, s.fbase, s.fok, s.srec, s.frag_cap, ctx->tabs, ea, 0u, 0ull, dres,
-                                          s.misc, 0ull, nblocks, (uint32_t)cus, s.wstart, s.xbal);
+    hipMemsetAsync(&s.misc.get()[M_DONE_CRC], 0, 8, st);  // the last workgroup finalizes
+    k_crc<0><<<cus, kCrcThreads, 0, st>>>(d, n, 40, nblocks, s.fbase.get(), s.fok.get(), s.srec.get(), s.frag_cap, ctx->tabs, ea, 0u, 0ull, dres,
+                                          s.misc.get(), 0ull, nblocks, (uint32_t)cus, s.wstart.get(), s.xbal.get());
   }, reps, st);
   printf("k_crc + finalize %.4f ms\n", as);
   {
     CK(bcw_decode_segment_async(ctx, d, &p, &t, dres));
     CK(hipStreamSynchronize(st));
     uint64_t m[16];
-    CK(hipMemcpy(m, s.misc, sizeof m, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(m, s.misc.get(), sizeof m, hipMemcpyDeviceToHost));
     int hz = 0;
     CK(hipDeviceGetAttribute(&hz, hipDeviceAttributeWallClockRate, 0));  // kHz
     printf("  stamps: first WG start -> finalize %.1f us (wall clock %d kHz)\n", (m[M_T_FIN] - m[M_T_CRC0]) * 1e3 / hz, hz);
