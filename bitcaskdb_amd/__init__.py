@@ -4,8 +4,8 @@ The product is libbcw.so (C-ABI in include/bcw.h, HIP kernels for gfx950 in csrc
 is the Python host mirror of the reference interface (wal.py: the WAL iterators, compaction re-encode,
 hint rebuild; index.py: the device-resident index, its rebuild from hint / data WALs, the device
 compaction filter and the batched Get by key against resident WALs; write.py: the batched Write into the
-active WAL's resident image; usage.py: live and freed bytes per WAL file for the compaction picker) and its ctypes
-binding (_lib.py).
+active WAL's resident image; usage.py: live and freed bytes per WAL file for the compaction picker; scrub.py: every
+index entry verified against the resident WALs) and its ctypes binding (_lib.py).
 """
 from . import _lib
 from .wal import (Context, Decoded, ErrCorruptedHintRecord, ErrInvalidData, ErrShortFile, ErrWalMismatchBlockSize,
@@ -17,6 +17,7 @@ from .index import (ErrKeyNotFound, ErrKeySoftDeleted, GetBatch, Index, WalSet, 
                     murmur3_sum64, recover_from_wals)
 from .write import ActiveWal, WriteBatch
 from .usage import FidUsage, FidUsageMap, PickerWalInfo, default_compaction_picker, drop_fids, wal_garbage
+from .scrub import BadEntry, ScrubReport, verify_index
 
 __all__ = ["Context", "Decoded", "ErrCorruptedHintRecord", "ErrInvalidData", "ErrShortFile",
            "ErrWalMismatchBlockSize", "ErrWalMismatchCRC", "ErrWalMismatchMagic", "ErrWalUnknownRecordType",
@@ -25,4 +26,4 @@ __all__ = ["Context", "Decoded", "ErrCorruptedHintRecord", "ErrInvalidData", "Er
            "new_hint_by_wal", "ErrKeyNotFound", "ErrKeySoftDeleted", "Index", "compact_one_wal_filtered",
            "merged_key", "murmur3_sum64", "recover_from_wals", "Stage", "WalSet", "GetBatch", "ActiveWal",
            "WriteBatch", "FidUsage", "PickerWalInfo", "default_compaction_picker", "wal_garbage",
-           "FidUsageMap", "drop_fids"]
+           "FidUsageMap", "drop_fids", "BadEntry", "ScrubReport", "verify_index"]

@@ -126,6 +126,23 @@ class UsageResult(C.Structure):
                 ("soft_deleted", C.c_uint64), ("invalid", C.c_uint64), ("fits", C.c_uint32), ("overflow", C.c_uint32)]
 
 
+class VerifyBad(C.Structure):
+    _fields_ = [("fid", C.c_uint64), ("off", C.c_uint64), ("size", C.c_uint64), ("hash", C.c_uint64),
+                ("key_pos", C.c_uint64), ("key_len", C.c_uint32), ("cls", C.c_uint8), ("rd_status", C.c_uint8),
+                ("rec_status", C.c_uint8), ("_pad", C.c_uint8)]
+
+
+class VerifyOut(C.Structure):
+    _fields_ = [("bad", C.c_void_p), ("bad_cap", C.c_uint64), ("keys", C.c_void_p), ("keys_cap", C.c_uint64),
+                ("rows", C.c_void_p), ("rows_cap", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class VerifyResult(C.Structure):
+    _fields_ = [("n_checked", C.c_uint64), ("n_soft_deleted", C.c_uint64), ("by_class", C.c_uint64 * 5),
+                ("by_rd", C.c_uint64 * 8), ("n_bad", C.c_uint64), ("bad_key_bytes", C.c_uint64),
+                ("per_fid", UsageResult), ("fits", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class IndexResult(C.Structure):
     _fields_ = [("n_in", C.c_uint64), ("n_done", C.c_uint64), ("err_class", C.c_int32), ("_pad", C.c_int32)]
 
@@ -192,6 +209,7 @@ DROP_IN, DROP_NOT_IN = 0, 1  # bcw_index_drop_fids* mode
 RECOVER_NOT_RUN, RECOVER_HINT, RECOVER_HINT_WAL, RECOVER_WAL = 0, 1, 2, 3
 RD_OK, RD_BEYOND, RD_CORRUPTED, RD_CRC, RD_SIZE, RD_TYPE, RD_INCOMPLETE, RD_PANIC = range(8)
 GET_OK, GET_NOT_FOUND, GET_SOFT_DELETED, GET_NO_WAL, GET_READ, GET_RECORD = range(6)
+VFY_OK, VFY_NO_WAL, VFY_READ, VFY_RECORD, VFY_KEY = range(5)  # bcw_index_verify*: the class of a checked entry
 
 
 def _load():
@@ -282,6 +300,8 @@ def _load():
         "bcw_index_drop_fids_async": (C.c_int, [vp, C.c_int, u64p, C.c_uint32, vp, C.c_uint32, vp]),
         "bcw_index_drop_fids": (C.c_int, [vp, C.c_int, u64p, C.c_uint32, C.POINTER(FidUsageRow), C.c_uint32,
                                           C.POINTER(UsageResult)]),
+        "bcw_index_verify_async": (C.c_int, [vp, vp, C.POINTER(GetParams), C.POINTER(VerifyOut), vp]),
+        "bcw_index_verify": (C.c_int, [vp, vp, C.POINTER(GetParams), C.POINTER(VerifyOut), C.POINTER(VerifyResult)]),
         "bcw_record_encode": (C.c_int64, [vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp,
                                           C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
         "bcw_write_bound": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64]),

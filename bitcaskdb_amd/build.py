@@ -7,7 +7,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRCS = [os.path.join(HERE, "csrc", f) for f in ("bcw_api.cpp", "bcw_decode.hip", "bcw_encode.hip", "bcw_fanout.cpp", "bcw_get.hip", "bcw_index.hip", "bcw_io.cpp", "bcw_put.hip", "bcw_read.hip", "bcw_usage.hip")]
+SRCS = [os.path.join(HERE, "csrc", f) for f in ("bcw_api.cpp", "bcw_decode.hip", "bcw_encode.hip", "bcw_fanout.cpp", "bcw_get.hip", "bcw_index.hip", "bcw_io.cpp", "bcw_put.hip", "bcw_read.hip", "bcw_usage.hip", "bcw_verify.hip")]
 OUT = os.path.join(HERE, "libbcw.so")
 ARCH = os.environ.get("BCW_OFFLOAD_ARCH", "gfx950")
 
@@ -34,7 +34,8 @@ def build(force: bool = False, verbose: bool = True, sanitize: bool = False) -> 
     deps = SRCS + [os.path.join(HERE, "csrc", h) for h in ("bcw_internal.h", "bcw_parse.h", "bcw_read_body.h",
                                                           "bcw_walset.h", "bcw_rules.h", "bcw_usage.h", "bcw_frame.h",
                                                           "bcw_crc_dev.h", "bcw_drop.h", "bcw_murmur.h", "bcw_host.h",
-                                                          "bcw_devmem.h", "bcw_crc_consts.h", "bcw_crc_tables.h")] + \
+                                                          "bcw_devmem.h", "bcw_crc_consts.h", "bcw_crc_tables.h",
+                                                          "bcw_verify.h")] + \
         [os.path.join(ROOT, "include", "bcw.h")]
     if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps):
         return out

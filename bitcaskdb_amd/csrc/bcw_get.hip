@@ -159,6 +159,14 @@ __global__ __launch_bounds__(64 * kWaves) void k_get_read(ReadArgs A) {
 }  // namespace get
 }  // namespace bcw
 
+namespace bcw {
+bcw_ctx* walset_ctx(const bcw_walset* ws) { return ws ? ws->ctx : nullptr; }
+const WalEnt* walset_device(const bcw_walset* ws, uint32_t* n_wals) {
+  *n_wals = (uint32_t)ws->t.ents.size();
+  return ws->d_ents.get();
+}
+}  // namespace bcw
+
 using namespace bcw;
 
 namespace {

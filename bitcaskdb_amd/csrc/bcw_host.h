@@ -124,6 +124,29 @@ struct GetLookup {
 };
 hipError_t ix_launch_get_lookup(bcw_index* x, const GetLookup& g, hipStream_t st);
 
+// The resident set as the kernels take it (bcw_get.hip): its context, and its device array (ascending fid) with
+// the number of entries, as of this call.
+bcw_ctx* walset_ctx(const bcw_walset* ws);
+const WalEnt* walset_device(const bcw_walset* ws, uint32_t* n_wals);
+
+// The select step of a scrub (bcw_verify.hip drives it; the kernel lives with the index, bcw_index.hip): one pass over
+// the slot table decides NO_WAL and READ / BEYOND, counts, and queues every other checked entry as a 48-byte work item
+// (vfy::Item, bcw_verify.h) for k_vfy_read. The launch grows the index's queue to its slot capacity, zeroes the call's
+// counters (cnt: vfy::V_NUM device words in front of the queue) and fills the last four fields: the index's buffers
+// are taken when the call is made, on the index's context.
+struct VerifySelect {
+  const WalEnt* wals;  // device, ascending fid
+  uint32_t n_wals;
+  bcw_verify_out out;  // the caller's arrays (device)
+  uint64_t* scratch;   // the context's accounting table (usage_begin)
+  // filled by the launch
+  unsigned long long* cnt;
+  void* queue;
+  uint64_t queue_cap;  // items; also the most the pass can queue
+  const uint8_t* arena;
+};
+int ix_launch_verify_select(bcw_index* x, VerifySelect& v, hipStream_t st);
+
 // The index half of a batched Write (bcw_put.hip drives it; the kernels live with the index, bcw_index.hip): the ops
 // of a write batch through the index's batch launches. Keys are the batch's merged keys; the number of ops is read
 // from the device word *n_in (n, or 0 when the batch was rejected), off / size from the device rec_off / rec_size, the

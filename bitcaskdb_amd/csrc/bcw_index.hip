@@ -46,6 +46,7 @@
 #include "bcw_read_body.h"
 #include "bcw_rules.h"
 #include "bcw_usage.h"
+#include "bcw_verify.h"
 
 namespace bcw {
 namespace ix {
@@ -565,6 +566,26 @@ __global__ __launch_bounds__(256) void k_ix_get(Src s, uint64_t n, const Slot* _
   status[i] = st;
 }
 
+// getWalRef (db_impl.go:589-593) and ReadRecord's span check (wal.go:562-564) of an index value (f, o, z), the one
+// text k_get_lookup and k_ix_vfy_select compile: the position of f in the resident set (ascending fid; n_wals: not
+// resident) and, when it is resident, *beyond. The value is not trusted: vfy::span_untrusted (bcw_verify.h) comes
+// before WalRecordSize's loop, which then runs at most seg_len / 32761 rounds and whose sum cannot wrap.
+__device__ __forceinline__ uint32_t wal_span(const WalEnt* __restrict__ wals, uint32_t n_wals, uint64_t f, uint64_t o,
+                                             uint64_t z, bool* beyond) {
+  uint32_t lo = 0, hi = n_wals;
+  while (lo < hi) {
+    const uint32_t m = (lo + hi) >> 1;
+    if (wals[m].fid < f) lo = m + 1; else hi = m;
+  }
+  *beyond = false;
+  if (lo >= n_wals || wals[lo].fid != f) return n_wals;
+  const uint64_t len = wals[lo].seg_len;
+  bool b = vfy::span_untrusted(o, z, len);
+  if (!b) b = vfy::span_beyond(o, rd::wal_record_size(o, z), len);  // no wrap: both terms are O(seg_len)
+  *beyond = b;
+  return lo;
+}
+
 // The lookup of a batched Get (DBImpl.Get, db_impl.go:567-577), one lane per flat key as k_ix_get: Index.Get, then
 // getWalRef -- the value's fid in the resident set, a binary search -- then ReadRecord's span check off +
 // WalRecordSize(off, size) > seg_len (wal.go:562-564). size comes out of the index and is not trusted: size > seg_len
@@ -590,24 +611,15 @@ __global__ __launch_bounds__(kGetLookupKeys) void k_get_lookup(Src s, GetLookup 
       if (o == 0) {
         gs = BCW_GET_SOFT_DELETED;
       } else {
-        uint32_t lo = 0, hi = g.n_wals;
-        while (lo < hi) {
-          const uint32_t m = (lo + hi) >> 1;
-          if (g.wals[m].fid < f) lo = m + 1; else hi = m;
-        }
-        if (lo >= g.n_wals || g.wals[lo].fid != f) {
+        bool beyond;
+        if (wal_span(g.wals, g.n_wals, f, o, z, &beyond) >= g.n_wals) {
           gs = BCW_GET_NO_WAL;
+        } else if (beyond) {
+          gs = BCW_GET_READ;
+          rs = BCW_RD_BEYOND;
         } else {
-          const uint64_t len = g.wals[lo].seg_len;
-          bool beyond = z > len || o < BCW_SUPER_BLOCK_SIZE || o > len;
-          if (!beyond) beyond = o + rd::wal_record_size(o, z) > len;  // no wrap: both terms are O(seg_len)
-          if (beyond) {
-            gs = BCW_GET_READ;
-            rs = BCW_RD_BEYOND;
-          } else {
-            gs = BCW_GET_OK;  // so far: k_get_read decides
-            slot = (z + 15) & ~15ull;
-          }
+          gs = BCW_GET_OK;  // so far: k_get_read decides
+          slot = (z + 15) & ~15ull;
         }
       }
     }
@@ -982,10 +994,12 @@ __device__ __forceinline__ uint32_t usage_chunk_pos(uint32_t slot, uint32_t q) {
 struct UsageLane {  // what a lane holds of its slot after a round; live is false for a lane past the table's end
   bool live;
   uint64_t fid, off, size;
+  uint64_t kref, hash;  // kKey rounds only (the scrub names the entry's key)
 };
 
 // one round: slots [base, base + 256) of the table (fewer at its end) through `stage` (kUsageSlots * 4 chunks), every
 // thread of the workgroup calls it; the lane's slot is base + threadIdx.x
+template <bool kKey = false>
 __device__ __forceinline__ UsageLane usage_round(const Slot* __restrict__ slots, uint64_t cap, uint64_t base,
                                                  uint4* __restrict__ stage) {
   const uint32_t tid = threadIdx.x;
@@ -1001,8 +1015,12 @@ __device__ __forceinline__ UsageLane usage_round(const Slot* __restrict__ slots,
   const bool valid = tid < nslots;
   const uint4 hf = stage[usage_chunk_pos(tid, 1)], os = stage[usage_chunk_pos(tid, 2)],
               lp = stage[usage_chunk_pos(tid, 3)];
+  uint4 ks = make_uint4(0, 0, 0, 0);
+  if (kKey) ks = stage[usage_chunk_pos(tid, 0)];
   __syncthreads();  // the next round overwrites the staging buffer
   UsageLane r;
+  r.kref = (uint64_t)ks.x | ((uint64_t)ks.y << 32);
+  r.hash = (uint64_t)hf.x | ((uint64_t)hf.y << 32);
   r.fid = (uint64_t)hf.z | ((uint64_t)hf.w << 32);
   r.off = (uint64_t)os.x | ((uint64_t)os.y << 32);
   r.size = (uint64_t)os.z | ((uint64_t)os.w << 32);
@@ -1091,6 +1109,114 @@ __global__ __launch_bounds__(usage::kThreads) void k_ix_drop(Slot* __restrict__ 
   if (tid == 0 && s_drop) atomicAdd(reinterpret_cast<unsigned long long*>(&cnt[C_LIVE]), 0ull - s_drop);
 }
 
+// ---- scrub, the select pass (bcw_index_verify*, bcw_verify.h): the reading twin that names keys ----------------------
+// The same rounds, with the slot's kref and hash. A live slot with off != 0 is checked: wal_span decides NO_WAL and
+// READ / BEYOND here (such an entry is emitted as bad, vfy::emit_bad, and feeds the accumulator by k_ix_usage's
+// counting rule), every other checked entry becomes a work item for k_vfy_read. The items of a wave are compacted by
+// ballot into the wave's own 64-item buffer in LDS; a buffer that cannot take a round's items goes to the queue first,
+// behind one reservation per wave (V_QUEUE), as 64 adjacent items. One reservation per wave and round was built
+// first and measured: at one key per 33 slots nearly every wave-round has an item, and the adds to the
+// one address took ten times the pass. A write past queue_cap, which the slot capacity never reaches, is dropped.
+// Order in the queue is unobservable and no workgroup waits for another. Index values are data here, never addresses:
+// only kref, which the index itself wrote, is followed. Counters are summed per lane, reduced per wave and added into
+// LDS; the workgroup adds each to its global word once, at the end (k_ix_drop's note).
+// the first n items of a wave's buffer to the queue, by the whole wave (n is wave-uniform)
+__device__ __forceinline__ void vfy_flush(const vfy::Item* __restrict__ buf, uint32_t n, unsigned long long* q_count,
+                                          vfy::Item* __restrict__ queue, uint64_t queue_cap, uint32_t lane) {
+  if (n == 0) return;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  unsigned long long q0 = 0;
+  if (lane == 0) q0 = atomicAdd(q_count, (unsigned long long)n);
+  const uint64_t pos = __shfl(q0, 0, 64) + lane;
+  if (lane < n && pos < queue_cap) queue[pos] = buf[lane];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the buffer is rewritten next
+  __builtin_amdgcn_wave_barrier();
+}
+
+__global__ __launch_bounds__(usage::kThreads) void k_ix_vfy_select(const Slot* __restrict__ slots, uint64_t cap,
+                                                                   const WalEnt* __restrict__ wals, uint32_t n_wals,
+                                                                   vfy::Sink S, vfy::Item* __restrict__ queue,
+                                                                   uint64_t queue_cap, uint64_t* __restrict__ scratch) {
+  __shared__ usage::Accum acc;
+  __shared__ uint4 stage[kUsageSlots * 4];
+  __shared__ unsigned long long s_cnt[5];  // checked, soft-deleted, invalid, NO_WAL, BEYOND
+  __shared__ __align__(16) vfy::Item s_q[usage::kThreads / 64][64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  vfy::Item* const wq = s_q[tid >> 6];
+  if (tid < 5) s_cnt[tid] = 0;
+  acc.init();
+  const usage::Table g = usage::table_of(scratch);
+  uint64_t n_chk = 0, n_soft = 0, n_inv = 0, n_nowal = 0, n_beyond = 0;
+  uint32_t nq = 0;  // items in the wave's buffer (wave-uniform)
+  for (uint64_t base = (uint64_t)blockIdx.x * kUsageSlots; base < cap; base += (uint64_t)gridDim.x * kUsageSlots) {
+    const UsageLane r = usage_round<true>(slots, cap, base, stage);
+    n_soft += (r.live && r.off == 0) ? 1 : 0;
+    const bool chk = r.live && r.off != 0;
+    if (__ballot(chk) == 0) continue;  // wave-uniform
+    uint32_t cls = BCW_VFY_OK, wal = 0, klen = 0;
+    if (chk) {
+      bool beyond;
+      wal = wal_span(wals, n_wals, r.fid, r.off, r.size, &beyond);
+      cls = vfy::classify(wal < n_wals, beyond ? BCW_RD_BEYOND : BCW_RD_OK, BCW_ST_OK, true);
+      klen = entry_len(S.arena, r.kref);
+      n_chk += 1;
+      n_nowal += cls == BCW_VFY_NO_WAL ? 1 : 0;
+      n_beyond += cls == BCW_VFY_READ ? 1 : 0;
+    }
+    const bool work = chk && cls == BCW_VFY_OK, bad = chk && cls != BCW_VFY_OK;
+    const uint64_t m = __ballot(work);
+    if (m) {
+      const uint32_t k = (uint32_t)__popcll(m);  // <= 64: an empty buffer always takes a round
+      if (nq + k > 64) {
+        vfy_flush(wq, nq, &S.cnt[vfy::V_QUEUE], queue, queue_cap, lane);
+        nq = 0;
+      }
+      if (work)
+        wq[nq + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] =
+            vfy::Item{r.fid, r.off, r.size, r.hash, r.kref, wal, klen};
+      nq += k;
+    }
+    if (__ballot(bad) == 0) continue;
+    const bool counted = bad && r.off >= BCW_SUPER_BLOCK_SIZE;
+    n_inv += (bad && !counted) ? 1 : 0;
+    if (bad)
+      vfy::emit_bad(S, r.fid, r.off, r.size, r.hash, r.kref, klen, cls, cls == BCW_VFY_READ ? BCW_RD_BEYOND : BCW_RD_OK,
+                    BCW_ST_OK);
+    const uint64_t span = counted ? usage::wal_record_size_closed(r.off, r.size) : 0;
+    acc.add(g, counted, r.fid, true, r.size, span);
+  }
+  vfy_flush(wq, nq, &S.cnt[vfy::V_QUEUE], queue, queue_cap, lane);
+  acc.flush(g);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    n_chk += __shfl_xor(n_chk, d, 64);
+    n_soft += __shfl_xor(n_soft, d, 64);
+    n_inv += __shfl_xor(n_inv, d, 64);
+    n_nowal += __shfl_xor(n_nowal, d, 64);
+    n_beyond += __shfl_xor(n_beyond, d, 64);
+  }
+  if (lane == 0) {
+    if (n_chk) atomicAdd(&s_cnt[0], (unsigned long long)n_chk);
+    if (n_soft) atomicAdd(&s_cnt[1], (unsigned long long)n_soft);
+    if (n_inv) atomicAdd(&s_cnt[2], (unsigned long long)n_inv);
+    if (n_nowal) atomicAdd(&s_cnt[3], (unsigned long long)n_nowal);
+    if (n_beyond) atomicAdd(&s_cnt[4], (unsigned long long)n_beyond);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    if (s_cnt[0]) atomicAdd(&S.cnt[vfy::V_CHECKED], s_cnt[0]);
+    if (s_cnt[1]) atomicAdd(&g.aux[usage::A_SOFT], s_cnt[1]);
+    if (s_cnt[2]) atomicAdd(&g.aux[usage::A_INVALID], s_cnt[2]);
+    if (s_cnt[3]) atomicAdd(&S.cnt[vfy::V_CLASS + BCW_VFY_NO_WAL], s_cnt[3]);
+    if (s_cnt[4]) {
+      atomicAdd(&S.cnt[vfy::V_CLASS + BCW_VFY_READ], s_cnt[4]);
+      atomicAdd(&S.cnt[vfy::V_RD + BCW_RD_BEYOND], s_cnt[4]);
+    }
+  }
+}
+
 }  // namespace ix
 }  // namespace bcw
 
@@ -1130,6 +1256,10 @@ struct bcw_index {
   uint64_t* drop_h = nullptr;
   DevBuf<uint64_t> drop_d;
   hipEvent_t drop_ev = nullptr;
+  // the scrub's counters and work queue (bcw_index_verify*; grow-only, allocated with the first scrub): vfy::V_NUM
+  // words, then one vfy::Item per slot of the table the queue was sized for
+  DevBuf<> vfy_q;
+  uint64_t vfy_q_cap = 0;
 };
 
 namespace {
@@ -1462,6 +1592,27 @@ int ix_usage_sync(bcw_index* x, bcw_fid_usage* h_rows, uint32_t cap, bcw_usage_r
 }  // namespace
 
 namespace bcw {
+int ix_launch_verify_select(bcw_index* x, VerifySelect& v, hipStream_t st) {
+  constexpr uint64_t kHead = vfy::V_NUM * sizeof(uint64_t);
+  if (x->cap > x->vfy_q_cap || !x->vfy_q) {
+    if (!x->vfy_q.reserve(kHead + x->cap * sizeof(vfy::Item), st)) {
+      x->vfy_q_cap = 0;
+      return BCW_E_NOMEM;
+    }
+    x->vfy_q_cap = x->cap;
+  }
+  v.cnt = static_cast<unsigned long long*>(x->vfy_q.get());
+  v.queue = v.cnt + vfy::V_NUM;
+  v.queue_cap = x->vfy_q_cap;
+  v.arena = x->arena;
+  if (hipMemsetAsync(v.cnt, 0, kHead, st) != hipSuccess) return BCW_E_HIP;
+  const vfy::Sink S{v.out, v.cnt, v.arena};
+  return ix_usage_pass(x, K_VFY_SELECT, st, [&](uint32_t grid) {
+    k_ix_vfy_select<<<grid, usage::kThreads, 0, st>>>(x->slots, x->cap, v.wals, v.n_wals, S,
+                                                      static_cast<vfy::Item*>(v.queue), v.queue_cap, v.scratch);
+  });
+}
+
 int ix_put_batch(bcw_index* x, const PutIx& p) {
   hipStream_t st = x->ctx->cur;
   if (p.n) {

@@ -1,5 +1,6 @@
 // bcw_read_body.h -- the per-request body of a point read, shared by k_read_records (bcw_read.hip: one WAL image,
-// caller-given payload offsets) and k_get_read (bcw_get.hip: each request against the image its index value names):
+// caller-given payload offsets), k_get_read (bcw_get.hip: each request against the image its index value names) and
+// k_vfy_read (bcw_verify.hip: every index entry against its image, nothing copied):
 // WalRecordSize (wal.go:61-86), WalParseRecord (wal.go:121-173: the fragment walk over the record's physical span,
 // optional CRC verify, size check) and RecordFromBytes (record.go:140-239). The mapping to the reference's errors
 // (BCW_RD_*, BCW_ST_*) lives here only.
@@ -123,7 +124,8 @@ __device__ __forceinline__ void copy_fragment(const ReadEnv& E, uint64_t ds, uin
 // size) and off + rs inside the image (the caller reports BCW_RD_BEYOND otherwise). All lanes of one wave; every
 // argument but `lane` is wave-uniform. Copies the record into out[0, size), records the first kMaxF fragments in E.fo /
 // E.fl (visible to the wave after the caller's wave barrier) and returns BCW_RD_*; nf: fragments walked.
-template <bool kWide>
+// kCopy = false (the scrub, k_vfy_read): the same walk with no byte stored; `out` is not read.
+template <bool kWide, bool kCopy = true>
 __device__ __forceinline__ uint32_t read_walk(const ReadEnv& E, uint64_t off, uint64_t size, uint64_t rs,
                                               uint8_t* __restrict__ out, uint32_t lane, uint32_t& nf) {
   const uint8_t* seg = E.seg;
@@ -146,7 +148,7 @@ __device__ __forceinline__ uint32_t read_walk(const ReadEnv& E, uint64_t off, ui
     ++nf;
     // copy what fits the payload slot (record = append(record, data...); a longer record is a size error)
     const uint64_t cl = got < size ? (len < size - got ? len : size - got) : 0;
-    copy_fragment<kWide>(E, ds, out + got, cl, lane);
+    if (kCopy) copy_fragment<kWide>(E, ds, out + got, cl, lane);
     if (E.verify) {
       // lane l: raw CRC-32C (init 0) of its chunk [l*c, min((l+1)*c, len)), shifted to the data end
       const uint64_t c = (len + 63) / 64;

@@ -859,8 +859,8 @@ int bcw_freed_by_fid_async(bcw_index* ix, uint64_t n, const uint8_t* d_found, co
  * `live` stays exact; only the rows and totals are void).
  * Async form: d_rows / d_res are device pointers; runs on the index's context stream without synchronising, the
  * index's buffers taken at launch (a drop queued after a batch sees the batch; a Put queued after the drop stays). One
- * caller at a time on the index; the accounting scratch is the context's, so one accounting or drop call at a time
- * per context. */
+ * caller at a time on the index; the accounting scratch is the context's, so one accounting, drop or scrub call at a
+ * time per context. */
 #define BCW_DROP_IN      0   /* drop entries whose fid is in the list (files that were deleted) */
 #define BCW_DROP_NOT_IN  1   /* drop entries whose fid is not in the list (keep only the files that exist) */
 int bcw_index_drop_fids_async(bcw_index* ix, int mode, const uint64_t* h_fids, uint32_t n_fids,
@@ -869,6 +869,81 @@ int bcw_index_drop_fids_async(bcw_index* ix, int mode, const uint64_t* h_fids, u
  * retried, so both are left to the caller to read from h_res (rows are copied only when they were written). */
 int bcw_index_drop_fids(bcw_index* ix, int mode, const uint64_t* h_fids, uint32_t n_fids,
                         bcw_fid_usage* h_rows, uint32_t cap, bcw_usage_result* h_res);
+
+/* ---- scrub: verify every index entry against the resident WALs ------------------------------------------------
+ * The index trusts where its values came from: a hint file (recoverFromWal db_impl.go:290-299, onePhase
+ * compaction.go:248-251) or a loaded snapshot puts (fid, off, size) as given, and nothing checks that the WAL bytes
+ * there still hold that key's record until somebody Gets the key -- and Get (db_impl.go:567-587) never compares the
+ * record's key with the key asked for, so an entry that points at another key's intact record returns the wrong value.
+ * One read-only pass answers "is this database consistent?" where the data already is: for every live, file-backed
+ * entry of the slot table, what DBImpl.Get of that key would run into, plus the key compare.
+ * A slot that is not live is ignored. A live entry with off == 0 (SoftDelete, index.go:125-142) names no record: it
+ * counts in n_soft_deleted and is not checked. Every other live entry is checked and gets exactly one class, decided
+ * in Get's order:
+ *   BCW_VFY_NO_WAL  the value's fid is not in the walset (getWalRef == nil, db_impl.go:574-577)
+ *   BCW_VFY_READ    Wal.ReadRecord / WalParseRecord fails; rd_status carries the BCW_RD_*. The index value is not
+ *                   trusted, by bcw_get_records*' rule: size > seg_len, off < 40, off > seg_len or off +
+ *                   WalRecordSize > seg_len is BCW_RD_BEYOND without WalRecordSize's loop being walked. With
+ *                   p->verify == 0 no CRC is computed (ReadOptions.VerifyChecksum)
+ *   BCW_VFY_RECORD  RecordFromBytes rejects the bytes; rec_status carries the BCW_ST_*
+ *   BCW_VFY_KEY     the record reads and parses, but payload[1, 1 + ns_size) || payload[hdr_size, hdr_size + key_len)
+ *                   is not the entry's merged key (the length or any byte differs): Get would return another key's
+ *                   value. The key is compared where the parse reads the header, in the record's first 64
+ *                   fragments (2 MiB); a key that reaches beyond them compares unequal
+ *   BCW_VFY_OK      none of the above
+ * The payload is never copied: the pass does a Get's reads and none of its stores.
+ * Output. The counts are exact whatever the caps. `bad` lists the entries whose class is not OK, in no particular
+ * order (as bcw_index_export), each with its merged key = keys[key_pos, key_pos + key_len), so the caller can
+ * bcw_index_apply Deletes (repair is the caller's). per_fid follows bcw_index_fid_usage's counting rule applied to
+ * the bad entries only: one row per fid with a bad entry whose off >= 40, ascending; bytes its size, span
+ * WalRecordSize in closed form; bad entries with 0 < off < 40 count in `invalid`; soft_deleted mirrors
+ * n_soft_deleted. The rows are what a Delete of the bad keys would free per file, and they name the damaged files.
+ * When bad_cap, keys_cap or rows_cap is too small (or per_fid.overflow is set: more than BCW_USAGE_MAX_FIDS fids with
+ * bad entries) fits is 0, the counts are still exact and the list, the key bytes and the rows are void; nothing was
+ * modified, so the caller asks again with n_bad, bad_key_bytes and per_fid.n_fids. NULL arrays with cap 0 give the
+ * totals only. */
+#define BCW_VFY_OK 0
+#define BCW_VFY_NO_WAL 1
+#define BCW_VFY_READ 2
+#define BCW_VFY_RECORD 3
+#define BCW_VFY_KEY 4
+typedef struct bcw_verify_bad {   /* one entry whose class != OK */
+  uint64_t fid, off, size;        /* the index value */
+  uint64_t hash;                  /* murmur3 Sum64 of the entry's merged key */
+  uint64_t key_pos;               /* the entry's merged key = keys[key_pos, key_pos + key_len) */
+  uint32_t key_len;
+  uint8_t cls, rd_status, rec_status, _pad;
+} bcw_verify_bad;                 /* 48 bytes */
+typedef struct bcw_verify_out {
+  bcw_verify_bad* bad;
+  uint64_t bad_cap;
+  uint8_t* keys;                  /* unpadded key bytes of the bad entries */
+  uint64_t keys_cap;
+  bcw_fid_usage* rows;
+  uint32_t rows_cap;
+  uint32_t _pad;
+} bcw_verify_out;
+typedef struct bcw_verify_result {
+  uint64_t n_checked, n_soft_deleted;
+  uint64_t by_class[5];           /* by BCW_VFY_*; sums to n_checked */
+  uint64_t by_rd[8];              /* the READ class by BCW_RD_*; by_rd[0] == 0 */
+  uint64_t n_bad, bad_key_bytes;  /* exact whatever the caps */
+  bcw_usage_result per_fid;       /* rows: one per fid with a bad entry, ascending */
+  uint32_t fits;                  /* 0: bad_cap, keys_cap or rows_cap too small */
+  uint32_t _pad;
+} bcw_verify_result;
+/* Async, device-resident: the arrays of *d_out and d_res are device pointers, the struct *d_out itself and p are host
+ * structs. Runs on the context's stream and does not synchronise; ix and ws must have been created on the same context
+ * (BCW_E_INVAL otherwise). Neither the index nor the set is modified; the index's buffers are taken at launch, as for
+ * bcw_get_records_async, so a scrub queued after a batch sees the batch. The work queue between the two passes is a
+ * grow-only buffer of the index, sized from its slot capacity. One caller at a time on the index; the accounting
+ * scratch is the context's, so one accounting, drop or scrub call at a time per context. */
+int bcw_index_verify_async(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p, const bcw_verify_out* d_out,
+                           bcw_verify_result* d_res);
+/* Synchronous, host out. Returns BCW_E_CAPACITY with the result filled (no list, key byte or row copied) when fits ==
+ * 0: retry with bad_cap = n_bad, keys_cap = bad_key_bytes, rows_cap = per_fid.n_fids. */
+int bcw_index_verify(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p, const bcw_verify_out* h_out,
+                     bcw_verify_result* h_res);
 
 /* ---- host I/O staging: WAL files <-> HBM through pinned slices ---------------------------------------
  * The reference reads a segment with PreadFull per 32 KiB block (utils.go:32-48, wal_iterator.go:55)
