@@ -404,13 +404,9 @@ int bcw_decode_fragments(bcw_ctx* c, const bcw_frag_table* h, uint64_t* n_total)
 static int ensure_dev_table(bcw_ctx* c, uint64_t cap) {
   if (cap <= c->d_tab.capacity && c->d_tab_mem) return BCW_OK;
   const uint64_t n = std::max<uint64_t>(cap, 1);
-  c->d_tab = bcw_record_table{};
-  Carver measure;
-  carve_table(measure, n, true);
-  if (!c->d_tab_mem.reserve(measure.total(), c->cur)) return BCW_E_NOMEM;
-  Carver cv(c->d_tab_mem.get(), measure.total());
-  c->d_tab = carve_table(cv, n, true);
-  return BCW_OK;
+  const int rc = carve_reserve(c->d_tab_mem, c->cur, [&](Carver& cv) { c->d_tab = carve_table(cv, n, true); });
+  if (rc != BCW_OK) c->d_tab = bcw_record_table{};
+  return rc;
 }
 
 // Upload the segment and decode it into the context's device table of `rows` rows, the fragment scratch retried until
@@ -536,20 +532,16 @@ bcw_decode_params src_params(const uint8_t* h_src, const bcw_encode_params* p) {
 int encode_run(bcw_ctx* c, const bcw_encode_params* p, const bcw_encode_out* h, bcw_encode_result* h_result,
                bcw_encode_out* d_out) {
   const uint64_t rows = c->d_tab.capacity;
-  Carver measure;
-  carve_encode_out(measure, rows, h->wal_cap, h->hint_cap);
-  if (!c->d_eout.reserve(measure.total(), c->cur)) return BCW_E_NOMEM;
-  Carver cv(c->d_eout.get(), c->d_eout.bytes());
-  bcw_encode_out& d = *d_out;
-  d = carve_encode_out(cv, rows, h->wal_cap, h->hint_cap);
-  if (!cv.ok()) return BCW_E_INVAL;
-  int rc = bcw_encode_segment_async(c, c->d_seg.get(), p, &c->d_tab, c->d_result.get(), c->d_keep.get(), &d,
-                                    c->d_eres.get());
+  bcw_encode_out d{};  // *d_out is written only once the carve is whole
+  int rc = carve_reserve(c->d_eout, c->cur, [&](Carver& cv) { d = carve_encode_out(cv, rows, h->wal_cap, h->hint_cap); });
+  if (rc != BCW_OK) return rc;
+  *d_out = d;
+  rc = bcw_encode_segment_async(c, c->d_seg.get(), p, &c->d_tab, c->d_result.get(), c->d_keep.get(), d_out,
+                                c->d_eres.get());
   if (rc != BCW_OK) return rc;
   HIPCHK(hipMemcpyAsync(h_result, c->d_eres.get(), sizeof *h_result, hipMemcpyDeviceToHost, c->cur));
   HIPCHK(hipStreamSynchronize(c->cur));
-  if (!h_result->fits) return BCW_E_CAPACITY;
-  if (h->rec_off && h->rec_off_cap < h_result->n_in) return BCW_E_CAPACITY;
+  if (!h_result->fits || (h->rec_off && h->rec_off_cap < h_result->n_in)) return BCW_E_CAPACITY;
   return BCW_OK;
 }
 

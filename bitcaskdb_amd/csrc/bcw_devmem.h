@@ -1,5 +1,7 @@
 // bcw_devmem.h -- host only: who owns a device allocation (DevBuf), how one allocation is cut into arrays (Carver), and
-// what is cut with it: the record table's column list, written once, and the layouts of the synchronous entry points.
+// what is cut with it: the record table's column list, written once, and every layout of the library: the synchronous
+// entry points' (fragments, read, get, put, encode outputs) and the index's (flat keys, apply, get, export, usage
+// rows, scrub queue).
 // The two types each hold one condition: an allocation is freed exactly once; the bytes allocated are the end of the
 // very walk that hands out the pointers. tools/devmem_check.cpp compiles this against stand-ins (BCW_DEVMEM_NO_HIP).
 #pragma once
@@ -37,10 +39,14 @@ class DevBuf {
     p_ = nullptr;
     bytes_ = 0;
   }
-  // frees what is held, then allocates `bytes` (> 0). false: nothing is held.
+  // frees what is held, then allocates `bytes` (> 0). false: nothing is held, and the failed call's error is taken
+  // off the thread, so that it is not found by a later check of a launch.
   bool alloc(uint64_t bytes) {
     reset();
-    if (hipMalloc(reinterpret_cast<void**>(&p_), bytes) != hipSuccess) p_ = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&p_), bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      p_ = nullptr;
+    }
     bytes_ = p_ ? bytes : 0;
     return p_ != nullptr;
   }
@@ -50,6 +56,13 @@ class DevBuf {
     if (bytes <= bytes_) return true;
     (void)hipStreamSynchronize(st);
     return alloc(bytes);
+  }
+  // replace: `nw` was allocated (and filled on `st`) while work queued on `st` could still read what is held, so the
+  // old allocation goes only once the stream has drained. Until the call nothing of *this has changed: a caller that
+  // fails before it simply returns, and its local `nw` frees itself.
+  void adopt(DevBuf&& nw, hipStream_t st) {
+    (void)hipStreamSynchronize(st);
+    *this = std::move(nw);
   }
 
  private:
@@ -136,6 +149,34 @@ int carve_alloc(DevBuf<>& mem, Layout&& layout) {
   layout(cv);
   return cv.ok() ? BCW_OK : BCW_E_INVAL;
 }
+// the same for a grow-only buffer (DevBuf::reserve on `st`). The limit of the carve is the measured total, not what
+// the buffer happens to hold: a layout whose second pass asks for more than its first is refused, not absorbed.
+template <class Layout>
+int carve_reserve(DevBuf<>& mem, hipStream_t st, Layout&& layout) {
+  Carver measure;
+  layout(measure);
+  if (!mem.reserve(measure.total(), st)) return BCW_E_NOMEM;
+  Carver cv(mem.get(), measure.total());
+  layout(cv);
+  return cv.ok() ? BCW_OK : BCW_E_INVAL;
+}
+
+// b bytes device -> host on `st`, unless there is nowhere to put them or nothing to copy; host -> device likewise
+inline bool copy_down(void* dst, const void* src, uint64_t b, hipStream_t st) {
+  return !dst || b == 0 || hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, st) == hipSuccess;
+}
+inline bool copy_up(void* dst, const void* src, uint64_t b, hipStream_t st) {
+  return b == 0 || hipMemcpyAsync(dst, src, b, hipMemcpyHostToDevice, st) == hipSuccess;
+}
+
+// the flat keys of a host call: key i = keys[key_off[i], key_off[i + 1])
+struct FlatKeys {
+  uint8_t* keys;
+  uint64_t* key_off;  // n + 1
+};
+inline FlatKeys carve_flat_keys(Carver& cv, uint64_t key_bytes, uint64_t n) {
+  return {cv.take_bytes16(key_bytes), cv.take<uint64_t>(n + 1)};  // a braced list: in this order
+}
 
 // bcw_decode_fragments: the export of n fragments
 inline bcw_frag_table carve_frags(Carver& cv, uint64_t n) {
@@ -171,17 +212,15 @@ inline ReadLayout carve_read(Carver& cv, uint64_t seg_len, uint64_t pay_bytes, u
 
 // bcw_get_records: the keys, the outputs (payload, lookup columns, optional table, the two status columns), the result
 struct GetLayout {
-  uint8_t* keys;
-  uint64_t* key_off;  // n + 1
+  FlatKeys k;
   bcw_get_out out;
   bcw_get_result* res;
 };
 inline GetLayout carve_get(Carver& cv, uint64_t key_bytes, uint64_t payload_cap, uint64_t n, bool tab) {
   GetLayout L{};
-  L.keys = cv.take_bytes16(key_bytes);
+  L.k = carve_flat_keys(cv, key_bytes, n);
   L.out.payload = cv.take_bytes16(payload_cap);
   L.out.payload_cap = payload_cap;
-  L.key_off = cv.take<uint64_t>(n + 1);
   L.out.fid = cv.take<uint64_t>(n);
   L.out.off = cv.take<uint64_t>(n);
   L.out.size = cv.take<uint64_t>(n);
@@ -237,6 +276,85 @@ inline bcw_encode_out carve_encode_out(Carver& cv, uint64_t rows, uint64_t wal_c
   d.hint_cap = hint_cap;
   cv.take<uint8_t>(kTailSlack);
   return d;
+}
+
+// ---- the index's layouts (bcw_index.hip) ----
+// bcw_index_apply_stat: the keys, the values, the two WriteStat columns (old fid, old size), the ops, found
+struct IxApplyLayout {
+  FlatKeys k;
+  uint64_t *fid, *off, *size, *free_fid, *free_bytes;
+  uint8_t *ops, *found;
+};
+inline IxApplyLayout carve_ix_apply(Carver& cv, uint64_t key_bytes, uint64_t n) {
+  IxApplyLayout L{};
+  L.k = carve_flat_keys(cv, key_bytes, n);
+  L.fid = cv.take<uint64_t>(n);
+  L.off = cv.take<uint64_t>(n);
+  L.size = cv.take<uint64_t>(n);
+  L.free_fid = cv.take<uint64_t>(n);
+  L.free_bytes = cv.take<uint64_t>(n);
+  L.ops = cv.take<uint8_t>(n);
+  L.found = cv.take<uint8_t>(n);
+  cv.take<uint8_t>(kTailSlack);
+  return L;
+}
+
+// bcw_index_get: the keys, the values, the status
+struct IxGetLayout {
+  FlatKeys k;
+  uint64_t *fid, *off, *size;
+  uint8_t* status;
+};
+inline IxGetLayout carve_ix_get(Carver& cv, uint64_t key_bytes, uint64_t n) {
+  IxGetLayout L{};
+  L.k = carve_flat_keys(cv, key_bytes, n);
+  L.fid = cv.take<uint64_t>(n);
+  L.off = cv.take<uint64_t>(n);
+  L.size = cv.take<uint64_t>(n);
+  L.status = cv.take<uint8_t>(n);
+  cv.take<uint8_t>(kTailSlack);
+  return L;
+}
+
+// ix_export: the nf selected fids, then per 256-slot block the entry count and the key bytes (phase one: tn = tb = 0;
+// phase two holds their exclusive prefixes there), then the tn entries with tb key bytes (phase two). The phase-one
+// part of both phases is the same, whatever follows it.
+struct IxExportLayout {
+  uint64_t *fids, *blk_n, *blk_b;
+  FlatKeys k;  // tn + 1 offsets
+  uint64_t *fid, *off, *size;
+};
+inline IxExportLayout carve_ix_export(Carver& cv, uint64_t nf, uint64_t nblk, uint64_t tn, uint64_t tb) {
+  IxExportLayout L{};
+  L.fids = cv.take<uint64_t>(nf, 16);
+  L.blk_n = cv.take<uint64_t>(nblk, 16);
+  L.blk_b = cv.take<uint64_t>(nblk);
+  if (tn) {
+    L.k = carve_flat_keys(cv, tb, tn);
+    L.fid = cv.take<uint64_t>(tn);
+    L.off = cv.take<uint64_t>(tn);
+    L.size = cv.take<uint64_t>(tn);
+  }
+  cv.take<uint8_t>(kTailSlack);
+  return L;
+}
+
+// bcw_index_fid_usage / bcw_index_drop_fids: the result, then cap rows (cap == 0: none)
+struct UsageLayout {
+  bcw_usage_result* res;
+  bcw_fid_usage* rows;
+};
+inline UsageLayout carve_usage(Carver& cv, uint64_t cap) {
+  return {cv.take<bcw_usage_result>(1, 16), cap ? cv.take<bcw_fid_usage>(cap, 16) : nullptr};
+}
+
+// the scrub: `words` counter words (vfy::V_NUM), then one work item of item_bytes (vfy::Item) per slot
+struct VfyQueueLayout {
+  unsigned long long* cnt;
+  void* queue;
+};
+inline VfyQueueLayout carve_vfy_queue(Carver& cv, uint64_t words, uint64_t slots, uint64_t item_bytes) {
+  return {cv.take<unsigned long long>(words, 16), cv.take<uint8_t>(slots * item_bytes, 16)};
 }
 
 }  // namespace bcw

@@ -179,8 +179,7 @@ int ws_publish(bcw_walset* ws) {
     const uint64_t cap = std::max<uint64_t>(16, std::max(n, ws->d_cap * 2));
     DevBuf<WalEnt> d;  // the new one first: the old copy stays valid when there is no room
     if (!d.alloc(cap * sizeof(WalEnt))) return BCW_E_NOMEM;
-    (void)hipStreamSynchronize(st);
-    ws->d_ents = std::move(d);
+    ws->d_ents.adopt(std::move(d), st);
     ws->d_cap = cap;
   }
   if (n && hipMemcpyAsync(ws->d_ents.get(), ws->t.ents.data(), n * sizeof(WalEnt), hipMemcpyHostToDevice, st) != hipSuccess)
@@ -284,8 +283,7 @@ int bcw_get_records_async(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p
     const uint64_t cap = std::max<uint64_t>(1024, std::max(nb, ws->blk_cap * 2));
     DevBuf<uint64_t> d;
     if (!d.alloc(2 * cap * sizeof(uint64_t))) return BCW_E_NOMEM;
-    (void)hipStreamSynchronize(st);
-    ws->d_blk = std::move(d);
+    ws->d_blk.adopt(std::move(d), st);
     ws->blk_cap = cap;
   }
   uint64_t* bsum = ws->d_blk.get();
@@ -342,35 +340,29 @@ int bcw_get_records(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p, uint
   *h_result = bcw_get_result{};
   h_result->fits = 1;
   if (n == 0) return BCW_OK;
-  const uint64_t kb = h_key_off[n] - h_key_off[0];
-  if (kb && !h_keys) return BCW_E_INVAL;
-  for (uint64_t i = 0; i < n; ++i)
-    if (h_key_off[i + 1] < h_key_off[i]) return BCW_E_INVAL;
+  if (const int rc = flat_keys_ok(n, h_keys, h_key_off)) return rc;
   bcw_ctx* c = ws->ctx;
   DeviceGuard dg(c->device);
   if (!dg.ok) return BCW_E_HIP;
   const bool tab = h.table.status != nullptr;
   DevBuf<> mem;
   GetLayout L;
+  const uint64_t kb = h_key_off[n] - h_key_off[0];
   if (const int rc = carve_alloc(mem, [&](Carver& cv) { L = carve_get(cv, kb, h.payload_cap, n, tab); })) return rc;
   const bcw_get_out& d = L.out;
   hipStream_t st = c->cur;
-  std::vector<uint64_t> koff(n + 1);
-  for (uint64_t i = 0; i <= n; ++i) koff[i] = h_key_off[i] - h_key_off[0];
-  auto down = [&](void* dst, const void* src, uint64_t b) {
-    return !dst || b == 0 || hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, st) == hipSuccess;
-  };
-  bool ok = (kb == 0 || hipMemcpyAsync(L.keys, h_keys + h_key_off[0], kb, hipMemcpyHostToDevice, st) == hipSuccess) &&
-            hipMemcpyAsync(L.key_off, koff.data(), 8 * (n + 1), hipMemcpyHostToDevice, st) == hipSuccess;
-  int rc = ok ? bcw_get_records_async(ix, ws, p, n, L.keys, L.key_off, &d, L.res) : BCW_E_HIP;
+  std::vector<uint64_t> koff;  // alive until the synchronise below
+  bool ok = upload_flat_keys(n, h_keys, h_key_off, L.k, st, &koff);
+  int rc = ok ? bcw_get_records_async(ix, ws, p, n, L.k.keys, L.k.key_off, &d, L.res) : BCW_E_HIP;
   if (rc == BCW_OK) {
-    ok = down(h_result, L.res, sizeof(bcw_get_result)) && down(h.get_status, d.get_status, n) &&
-         down(h.rd_status, d.rd_status, n) && down(h.fid, d.fid, 8 * n) && down(h.off, d.off, 8 * n) &&
-         down(h.size, d.size, 8 * n) && down(h.pay_off, d.pay_off, 8 * n) && hipStreamSynchronize(st) == hipSuccess;
+    ok = copy_down(h_result, L.res, sizeof(bcw_get_result), st) && copy_down(h.get_status, d.get_status, n, st) &&
+         copy_down(h.rd_status, d.rd_status, n, st) && copy_down(h.fid, d.fid, 8 * n, st) &&
+         copy_down(h.off, d.off, 8 * n, st) && copy_down(h.size, d.size, 8 * n, st) &&
+         copy_down(h.pay_off, d.pay_off, 8 * n, st) && hipStreamSynchronize(st) == hipSuccess;
     rc = !ok ? BCW_E_HIP : h_result->fits ? BCW_OK : BCW_E_CAPACITY;
   }
   if (rc == BCW_OK) {
-    ok = down(h.payload, d.payload, h_result->payload_need);
+    ok = copy_down(h.payload, d.payload, h_result->payload_need, st);
     if (ok && tab) ok = table_copy_down(h.table, d.table, std::min(n, h.table.capacity), st);
     ok = ok && hipStreamSynchronize(st) == hipSuccess;
     if (!ok) rc = BCW_E_HIP;

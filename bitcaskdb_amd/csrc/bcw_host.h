@@ -83,6 +83,25 @@ struct DeviceGuard {
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
+// The flat keys of a host call, key i = h_keys[h_key_off[i], h_key_off[i + 1]), n > 0 (bcw_index_apply_stat,
+// bcw_index_get, bcw_get_records). flat_keys_ok refuses offsets that run backwards and a NULL h_keys with key bytes.
+// upload_flat_keys queues the two copies into d (carve_flat_keys): the key bytes from the first key on, and the
+// offsets rebased to it, which *koff holds until the caller has synchronised `st`.
+inline int flat_keys_ok(uint64_t n, const uint8_t* h_keys, const uint64_t* h_key_off) {
+  if (h_key_off[n] != h_key_off[0] && !h_keys) return BCW_E_INVAL;
+  for (uint64_t i = 0; i < n; ++i)
+    if (h_key_off[i + 1] < h_key_off[i]) return BCW_E_INVAL;
+  return BCW_OK;
+}
+inline bool upload_flat_keys(uint64_t n, const uint8_t* h_keys, const uint64_t* h_key_off, const FlatKeys& d,
+                             hipStream_t st, std::vector<uint64_t>* koff) {
+  const uint64_t kb = h_key_off[n] - h_key_off[0];
+  koff->resize(n + 1);
+  for (uint64_t i = 0; i <= n; ++i) (*koff)[i] = h_key_off[i] - h_key_off[0];
+  return copy_up(d.keys, kb ? h_keys + h_key_off[0] : nullptr, kb, st) &&
+         copy_up(d.key_off, koff->data(), 8 * (n + 1), st);
+}
+
 // The context an index was created on (bcw_index.hip): the sync entry points refuse an index of another context.
 bcw_ctx* index_ctx(const bcw_index* ix);
 // doFilter (bcw_compact_filter_async) of context c's latest decode against index x, on c's stream, with the call's

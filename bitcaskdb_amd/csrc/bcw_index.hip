@@ -1225,20 +1225,19 @@ using namespace bcw::ix;
 
 struct bcw_index {
   bcw_ctx* ctx = nullptr;
-  Slot* slots = nullptr;
+  DevBuf<Slot> slots;
   uint64_t cap = 0;  // slots (power of two)
-  uint8_t* arena = nullptr;
-  uint64_t arena_cap = 0;
-  uint64_t* cnt = nullptr;  // device counters
+  DevBuf<uint8_t> arena;  // the key arena; arena.bytes() is its capacity
+  DevBuf<uint64_t> cnt;  // device counters
   uint64_t slots_ub = 0, arena_ub = 0;  // host upper bounds of the device counters
   uint64_t seq_base = 1;                // sequence number of the next op
   uint64_t limited = 0;                 // the capacity bound (bcw_index_set_limit; 0: none)
-  // per-op scratch
-  DevBuf<uint64_t> op_kref, op_hash, op_slot;  // [op_cap] each
+  // per-op scratch: one allocation, three arrays of op_cap entries
+  DevBuf<> op_mem;
+  struct { uint64_t *kref, *hash, *slot; } op{};
   uint64_t op_cap = 0;
-  // host-batch staging (device copies)
+  // host-batch staging (device copies), carved anew by every call (bcw_devmem.h)
   DevBuf<> stage;
-  bcw_index_result* d_res = nullptr;
   // compaction filter rules (bcw_index_set_compact_rules): the host copy (mask 0: none; the prefix arrays point into
   // the two vectors), the packed prefix table and the counters on the device (allocated with the first rules: three
   // cumulative words, then the three of a synchronous compaction in progress, k_ix_rule_commit), and the counts
@@ -1247,8 +1246,8 @@ struct bcw_index {
   std::vector<uint8_t> rule_bytes;
   std::vector<uint32_t> rule_off;
   uint32_t rule_longest = 0;
-  rules::PrefixTable* d_rule_tab = nullptr;
-  uint64_t* d_rule_cnt = nullptr;
+  DevBuf<rules::PrefixTable> d_rule_tab;
+  DevBuf<uint64_t> d_rule_cnt;
   uint64_t rule_host[3] = {0, 0, 0};
   // the fid list of bcw_index_drop_fids* (allocated with the first drop, BCW_USAGE_MAX_FIDS entries each): the
   // normalised list in pinned host memory, its device copy, and the event behind the last copy out of the pinned
@@ -1256,8 +1255,8 @@ struct bcw_index {
   uint64_t* drop_h = nullptr;
   DevBuf<uint64_t> drop_d;
   hipEvent_t drop_ev = nullptr;
-  // the scrub's counters and work queue (bcw_index_verify*; grow-only, allocated with the first scrub): vfy::V_NUM
-  // words, then one vfy::Item per slot of the table the queue was sized for
+  // the scrub's counters and work queue (bcw_index_verify*; grow-only, allocated with the first scrub), carved for
+  // the vfy_q_cap slots of the largest table a scrub has met (carve_vfy_queue)
   DevBuf<> vfy_q;
   uint64_t vfy_q_cap = 0;
 };
@@ -1281,7 +1280,7 @@ hipError_t ix_launch_get_lookup(bcw_index* x, const GetLookup& g, hipStream_t st
   if (g.n == 0) return hipSuccess;
   const Src s = flat_src(g.keys, g.koff, 0);  // keys_len: the kernel reads koff[n]
   k_get_lookup<<<(uint32_t)((g.n + kGetLookupKeys - 1) / kGetLookupKeys), kGetLookupKeys, 0, st>>>(
-      s, g, x->slots, x->cap - 1, x->arena);
+      s, g, x->slots.get(), x->cap - 1, x->arena.get());
   return hipGetLastError();
 }
 }  // namespace bcw
@@ -1297,10 +1296,9 @@ uint64_t pow2_at_least(uint64_t v) {
 }
 
 int ix_sync_counters(bcw_index* x, uint64_t* out) {
-  if (hipMemcpyAsync(out, x->cnt, C_NUM * sizeof(uint64_t), hipMemcpyDeviceToHost, x->ctx->cur) != hipSuccess ||
-      hipStreamSynchronize(x->ctx->cur) != hipSuccess)
-    return BCW_E_HIP;
-  return BCW_OK;
+  hipStream_t st = x->ctx->cur;
+  const bool ok = copy_down(out, x->cnt.get(), C_NUM * sizeof(uint64_t), st) && hipStreamSynchronize(st) == hipSuccess;
+  return ok ? BCW_OK : BCW_E_HIP;
 }
 
 // the host's upper bounds, made exact from counters just read (c: ix_sync_counters)
@@ -1312,72 +1310,59 @@ void ix_refresh_bounds(bcw_index* x, const uint64_t* c) {
 // three adjacent counters from `first` (cnt + C_NIN, cnt + C_R_ARENA, or the rules' three) to zero
 hipError_t zero_group(uint64_t* first, hipStream_t st) { return hipMemsetAsync(first, 0, 3 * sizeof(uint64_t), st); }
 
-// grow the slot table to hold `slots` claimed slots at kMaxLoad and the arena to `arena` bytes
+// grow the slot table to hold `slots` claimed slots at kMaxLoad and the arena to `arena` bytes. The larger buffer is
+// built in a local on the stream and adopted once the stream has drained (DevBuf::adopt): queued work reads the old
+// one until then, and a failure returns with the index as it was.
 int ix_grow(bcw_index* x, uint64_t slots, uint64_t arena) {
   hipStream_t st = x->ctx->cur;
-  if (arena > x->arena_cap) {
-    const uint64_t na = std::max(arena, x->arena_cap * 2);
-    uint8_t* a = nullptr;
-    if (hipMalloc(&a, na) != hipSuccess) return BCW_E_NOMEM;
-    if (x->arena && hipMemcpyAsync(a, x->arena, x->arena_ub < x->arena_cap ? x->arena_ub : x->arena_cap,
-                                   hipMemcpyDeviceToDevice, st) != hipSuccess) {
-      (void)hipFree(a);
+  if (arena > x->arena.bytes()) {
+    const uint64_t na = std::max(arena, x->arena.bytes() * 2);
+    DevBuf<uint8_t> a;
+    if (!a.alloc(na)) return BCW_E_NOMEM;
+    if (x->arena && hipMemcpyAsync(a.get(), x->arena.get(), std::min(x->arena_ub, x->arena.bytes()),
+                                   hipMemcpyDeviceToDevice, st) != hipSuccess)
       return BCW_E_HIP;
-    }
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(x->arena);
-    x->arena = a;
-    x->arena_cap = na;
+    x->arena.adopt(std::move(a), st);
   }
   const uint64_t want = pow2_at_least((uint64_t)((double)slots / kMaxLoad) + 1);
   if (want > x->cap) {
-    Slot* ns = nullptr;
-    if (hipMalloc(&ns, want * sizeof(Slot)) != hipSuccess) return BCW_E_NOMEM;
-    if (hipMemsetAsync(ns, 0, want * sizeof(Slot), st) != hipSuccess) { (void)hipFree(ns); return BCW_E_HIP; }
+    DevBuf<Slot> ns;
+    if (!ns.alloc(want * sizeof(Slot))) return BCW_E_NOMEM;
+    if (hipMemsetAsync(ns.get(), 0, want * sizeof(Slot), st) != hipSuccess) return BCW_E_HIP;
     if (x->slots && x->cap)
-      k_ix_rehash<<<(uint32_t)((x->cap + 255) / 256), 256, 0, st>>>(x->slots, x->cap, ns, want - 1);
-    if (hipStreamSynchronize(st) != hipSuccess) { (void)hipFree(ns); return BCW_E_HIP; }
-    (void)hipFree(x->slots);
-    x->slots = ns;
+      k_ix_rehash<<<(uint32_t)((x->cap + 255) / 256), 256, 0, st>>>(x->slots.get(), x->cap, ns.get(), want - 1);
+    if (hipStreamSynchronize(st) != hipSuccess) return BCW_E_HIP;
+    x->slots.adopt(std::move(ns), st);  // the stream is empty by now: adopt's own synchronise returns at once
     x->cap = want;
   }
   return BCW_OK;
 }
 
 // rebuild the index from its live keys only (k_ix_compact) into a table of ncap slots and an arena of narena bytes,
-// both large enough for them; the old buffers are freed after the stream sync, as in ix_grow. On an error the index
-// is left as it was.
+// both large enough for them; the new buffers are adopted after the stream sync, as in ix_grow. On an error the index
+// is left as it was: the rebuild counts in the C_R_* counters, which k_ix_adopt moves over only when it succeeded.
 int ix_compact(bcw_index* x, uint64_t ncap, uint64_t narena) {
   hipStream_t st = x->ctx->cur;
-  Slot* ns = nullptr;
-  uint8_t* na = nullptr;
-  if (hipMalloc(&ns, ncap * sizeof(Slot)) != hipSuccess || hipMalloc(&na, narena) != hipSuccess) {
-    (void)hipGetLastError();
-    (void)hipFree(ns);
-    return BCW_E_NOMEM;
-  }
+  DevBuf<Slot> ns;
+  DevBuf<uint8_t> na;
+  if (!ns.alloc(ncap * sizeof(Slot)) || !na.alloc(narena)) return BCW_E_NOMEM;
   uint64_t c[C_NUM];
-  bool ok = hipMemsetAsync(ns, 0, ncap * sizeof(Slot), st) == hipSuccess &&
-            zero_group(x->cnt + C_R_ARENA, st) == hipSuccess;
+  bool ok = hipMemsetAsync(ns.get(), 0, ncap * sizeof(Slot), st) == hipSuccess &&
+            zero_group(x->cnt.get() + C_R_ARENA, st) == hipSuccess;
   if (ok)
-    k_ix_compact<<<(uint32_t)((x->cap + 255) / 256), 256, 0, st>>>(x->slots, x->cap, x->arena, x->arena_cap, ns,
-                                                                   ncap - 1, na, narena, x->cnt);
+    k_ix_compact<<<(uint32_t)((x->cap + 255) / 256), 256, 0, st>>>(x->slots.get(), x->cap, x->arena.get(),
+                                                                   x->arena.bytes(), ns.get(), ncap - 1, na.get(),
+                                                                   narena, x->cnt.get());
   ok = ok && hipGetLastError() == hipSuccess && ix_sync_counters(x, c) == BCW_OK && c[C_R_FAIL] == 0;
   if (ok) {
-    k_ix_adopt<<<1, 1, 0, st>>>(x->cnt);
+    k_ix_adopt<<<1, 1, 0, st>>>(x->cnt.get());
     ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
   }
-  if (!ok) {
-    (void)hipFree(ns);
-    (void)hipFree(na);
-    return BCW_E_HIP;
-  }
-  (void)hipFree(x->slots);
-  (void)hipFree(x->arena);
-  x->slots = ns;
+  if (!ok) return BCW_E_HIP;
+  // the stream is empty by now (the checked synchronise above): the synchronise inside each adopt returns at once
+  x->slots.adopt(std::move(ns), st);
+  x->arena.adopt(std::move(na), st);
   x->cap = ncap;
-  x->arena = na;
-  x->arena_cap = narena;
   x->slots_ub = c[C_R_SLOTS];
   x->arena_ub = c[C_R_ARENA];
   return BCW_OK;
@@ -1390,7 +1375,7 @@ int ix_compact(bcw_index* x, uint64_t ncap, uint64_t narena) {
 // only if the batch still does not fit. A batch that fits costs no sync and no launch here.
 int ix_room(bcw_index* x, uint64_t n, uint64_t arena_bytes) {
   const auto fits = [&] {
-    return (double)(x->slots_ub + n) <= kMaxLoad * (double)x->cap && x->arena_ub + arena_bytes <= x->arena_cap;
+    return (double)(x->slots_ub + n) <= kMaxLoad * (double)x->cap && x->arena_ub + arena_bytes <= x->arena.bytes();
   };
   if (!fits()) {
     uint64_t c[C_NUM];
@@ -1399,7 +1384,7 @@ int ix_room(bcw_index* x, uint64_t n, uint64_t arena_bytes) {
     if (c[C_OVERFLOW]) return BCW_E_CAPACITY;  // a previous batch overflowed: the index is inconsistent
     ix_refresh_bounds(x, c);
     if (c[C_SLOTS] > 0 && c[C_SLOTS] - c[C_LIVE] >= c[C_SLOTS] / 2) {
-      rc = ix_compact(x, x->cap, x->arena_cap);
+      rc = ix_compact(x, x->cap, x->arena.bytes());
       if (rc != BCW_OK) return rc;
     }
     if (!fits()) {
@@ -1408,54 +1393,27 @@ int ix_room(bcw_index* x, uint64_t n, uint64_t arena_bytes) {
     }
   }
   if (n > x->op_cap) {
-    (void)hipStreamSynchronize(x->ctx->cur);
-    x->op_kref.reset();
-    x->op_hash.reset();
-    x->op_slot.reset();
-    x->op_cap = 0;
     const uint64_t c = std::max<uint64_t>(n, 1024);
-    if (!x->op_kref.alloc(c * 8) || !x->op_hash.alloc(c * 8) || !x->op_slot.alloc(c * 8)) return BCW_E_NOMEM;
-    x->op_cap = c;
+    const int rc = carve_reserve(x->op_mem, x->ctx->cur, [&](Carver& cv) {
+      x->op = {cv.take<uint64_t>(c), cv.take<uint64_t>(c), cv.take<uint64_t>(c)};
+    });
+    x->op_cap = rc == BCW_OK ? c : 0;
+    if (rc != BCW_OK) return rc;
   }
   x->slots_ub += n;
   x->arena_ub += arena_bytes;
   return BCW_OK;
 }
 
-int ix_stage(bcw_index* x, uint64_t bytes) {
-  return x->stage.reserve(bytes, x->ctx->cur) ? BCW_OK : BCW_E_NOMEM;
-}
-
-// The flat keys of a host call, key i = h_keys[h_key_off[i], h_key_off[i + 1]), n > 0: flat_keys_ok refuses offsets
-// that run backwards and a NULL h_keys with key bytes; stage_flat_keys sizes x->stage for keys | offsets rebased to
-// the first key | `rest` bytes of the caller's own, and queues the copies of the first two.
-struct FlatStage {
-  Src src;                     // the staged keys
-  uint8_t* rest;               // device, 8-byte aligned: the caller's part of the staging buffer
-  std::vector<uint64_t> koff;  // the rebased offsets the copy reads: alive until the caller has synchronised
-};
-int flat_keys_ok(uint64_t n, const uint8_t* h_keys, const uint64_t* h_key_off) {
-  if (h_key_off[n] != h_key_off[0] && !h_keys) return BCW_E_INVAL;
-  for (uint64_t i = 0; i < n; ++i)
-    if (h_key_off[i + 1] < h_key_off[i]) return BCW_E_INVAL;
-  return BCW_OK;
-}
-int stage_flat_keys(bcw_index* x, uint64_t n, const uint8_t* h_keys, const uint64_t* h_key_off, uint64_t rest,
-                    FlatStage* f) {
-  const uint64_t kb = h_key_off[n] - h_key_off[0], kbp = (kb + 15) & ~15ull;
-  const int rc = ix_stage(x, kbp + 8 * (n + 1) + rest + 64);
-  if (rc != BCW_OK) return rc;
-  uint8_t* d_keys = (uint8_t*)x->stage.get();
-  uint64_t* d_koff = (uint64_t*)(d_keys + kbp);
+// x->stage carved by a layout that begins with the flat keys of a host call (carve_ix_apply, carve_ix_get: *L), and
+// the copies of the keys queued (flat_keys_ok, upload_flat_keys: bcw_host.h). *koff lives until the caller's sync.
+template <class Layout>
+int stage_flat_keys(bcw_index* x, uint64_t n, const uint8_t* h_keys, const uint64_t* h_key_off,
+                    Layout (*carve)(Carver&, uint64_t, uint64_t), Layout* L, std::vector<uint64_t>* koff) {
   hipStream_t st = x->ctx->cur;
-  f->koff.resize(n + 1);
-  for (uint64_t i = 0; i <= n; ++i) f->koff[i] = h_key_off[i] - h_key_off[0];
-  if ((kb && hipMemcpyAsync(d_keys, h_keys + h_key_off[0], kb, hipMemcpyHostToDevice, st) != hipSuccess) ||
-      hipMemcpyAsync(d_koff, f->koff.data(), 8 * (n + 1), hipMemcpyHostToDevice, st) != hipSuccess)
-    return BCW_E_HIP;
-  f->src = flat_src(d_keys, d_koff, kb);
-  f->rest = (uint8_t*)(d_koff + (n + 1));
-  return BCW_OK;
+  const int rc = carve_reserve(x->stage, st, [&](Carver& cv) { *L = carve(cv, h_key_off[n] - h_key_off[0], n); });
+  if (rc != BCW_OK) return rc;
+  return upload_flat_keys(n, h_keys, h_key_off, L->k, st, koff) ? BCW_OK : BCW_E_HIP;
 }
 
 // the capacity bound after a batch (k_ix_evict), when one is set
@@ -1463,7 +1421,7 @@ void ix_bound(bcw_index* x) {
   if (!x->limited) return;
   uint32_t npass = 1;
   while (npass < 6 && (x->seq_base >> (11u * npass)) != 0) ++npass;  // digits of the largest sequence number
-  k_ix_evict<<<16, 1024, 0, x->ctx->cur>>>(x->slots, x->cap, x->limited / 16, x->cnt, npass);
+  k_ix_evict<<<16, 1024, 0, x->ctx->cur>>>(x->slots.get(), x->cap, x->limited / 16, x->cnt.get(), npass);
 }
 
 // the five launches of a batch (ops [0, n) of src); old_*: optional WriteStat outputs of k_ix_claim
@@ -1471,14 +1429,15 @@ void ix_batch(bcw_index* x, const Src& s, uint64_t n, const bcw_decode_result* R
               uint8_t* old_found = nullptr, uint64_t* old_fid = nullptr, uint64_t* old_size = nullptr) {
   hipStream_t st = x->ctx->cur;
   const uint32_t grid = (uint32_t)((n + 255) / 256);
-  (void)zero_group(x->cnt + C_NIN, st);
+  (void)zero_group(x->cnt.get() + C_NIN, st);
   if (!grid) return;
-  k_ix_keys<<<grid, 256, 0, st>>>(s, n, R, gen, x->cnt, x->op_kref.get(), x->op_hash.get());
-  k_ix_claim<<<grid, 256, 0, st>>>(s, n, x->cnt, x->slots, x->cap - 1, x->arena, x->cnt, x->op_kref.get(),
-                                   x->op_hash.get(), x->op_slot.get(), old_found, old_fid, old_size);
-  k_ix_seq<<<grid, 256, 0, st>>>(n, x->cnt, s.kind == SRC_FLAT, x->slots, x->op_slot.get(), x->seq_base);
-  k_ix_commit<<<grid, 256, 0, st>>>(s, n, x->cnt, x->slots, x->arena, x->arena_cap, x->op_hash.get(), x->op_slot.get());
-  k_ix_write<<<grid, 256, 0, st>>>(s, n, x->cnt, v, x->slots, x->op_slot.get(), x->seq_base);
+  k_ix_keys<<<grid, 256, 0, st>>>(s, n, R, gen, x->cnt.get(), x->op.kref, x->op.hash);
+  k_ix_claim<<<grid, 256, 0, st>>>(s, n, x->cnt.get(), x->slots.get(), x->cap - 1, x->arena.get(), x->cnt.get(),
+                                   x->op.kref, x->op.hash, x->op.slot, old_found, old_fid, old_size);
+  k_ix_seq<<<grid, 256, 0, st>>>(n, x->cnt.get(), s.kind == SRC_FLAT, x->slots.get(), x->op.slot, x->seq_base);
+  k_ix_commit<<<grid, 256, 0, st>>>(s, n, x->cnt.get(), x->slots.get(), x->arena.get(), x->arena.bytes(), x->op.hash,
+                                    x->op.slot);
+  k_ix_write<<<grid, 256, 0, st>>>(s, n, x->cnt.get(), v, x->slots.get(), x->op.slot, x->seq_base);
   x->seq_base += n;
   ix_bound(x);
 }
@@ -1509,15 +1468,16 @@ int ix_launch_filter(bcw_index* x, const Src& s, uint64_t rows, const bcw_decode
   if (!rows) return BCW_OK;
   const uint32_t grid = (uint32_t)((rows + 255) / 256);
   if (!x->rules.mask) {
-    k_ix_filter<<<grid, 256, 0, st>>>(s, rows, d_result, gen, x->slots, x->cap - 1, x->arena, src_fid, d_keep, cnt);
+    k_ix_filter<<<grid, 256, 0, st>>>(s, rows, d_result, gen, x->slots.get(), x->cap - 1, x->arena.get(), src_fid,
+                                      d_keep, cnt);
     return BCW_OK;
   }
   if (!s.t.expire || !s.t.flags) return BCW_E_INVAL;
   const bool pfx = (x->rules.mask & BCW_RULE_PREFIX) != 0;
-  const Rules ru{x->rules.mask, pfx ? x->rules.n_prefix : 0u, pfx ? x->rule_longest : 0u, x->rules.now, x->d_rule_tab,
-                 rule_cnt};
-  k_ix_filter_rules<<<grid, 256, 0, st>>>(s, rows, d_result, gen, x->slots, x->cap - 1, x->arena, src_fid, d_keep, cnt,
-                                          ru);
+  const Rules ru{x->rules.mask, pfx ? x->rules.n_prefix : 0u, pfx ? x->rule_longest : 0u, x->rules.now,
+                 x->d_rule_tab.get(), rule_cnt};
+  k_ix_filter_rules<<<grid, 256, 0, st>>>(s, rows, d_result, gen, x->slots.get(), x->cap - 1, x->arena.get(), src_fid,
+                                          d_keep, cnt, ru);
   return BCW_OK;
 }
 
@@ -1533,7 +1493,8 @@ int ix_filter(bcw_index* x, bcw_ctx* c, const uint8_t* d_seg, const bcw_decode_p
   DeviceGuard dg(c->device);
   if (!dg.ok) return BCW_E_HIP;
   hipStream_t st = c->cur;
-  if (cnt != x->cnt) (void)hipMemcpyAsync(cnt, x->cnt, C_NUM * sizeof(uint64_t), hipMemcpyDeviceToDevice, st);
+  if (cnt != x->cnt.get())
+    (void)hipMemcpyAsync(cnt, x->cnt.get(), C_NUM * sizeof(uint64_t), hipMemcpyDeviceToDevice, st);
   (void)zero_group(cnt + C_NIN, st);
   if (zero_rules) (void)zero_group(rule_cnt, st);
   const Src s = table_src(c, d_seg, p, d_table, SRC_RECORD);
@@ -1548,7 +1509,7 @@ int ix_filter(bcw_index* x, bcw_ctx* c, const uint8_t* d_seg, const bcw_decode_p
 // buffers are taken as they are now: a batch queued before this call has already grown them.
 template <class Launch>
 int ix_usage_pass(bcw_index* x, int kid, hipStream_t st, Launch&& launch) {
-  if (!x->slots || !x->cap) return BCW_OK;
+  if (!x->slots.get() || !x->cap) return BCW_OK;
   bcw_ctx* c = x->ctx;
   const uint64_t wgs = (x->cap + kUsageSlots - 1) / kUsageSlots;
   const uint32_t grid = (uint32_t)std::min<uint64_t>(wgs, (uint64_t)c->num_cus * 8);
@@ -1560,8 +1521,9 @@ int ix_usage_pass(bcw_index* x, int kid, hipStream_t st, Launch&& launch) {
 }
 
 // The synchronous form of bcw_index_fid_usage_async / bcw_index_drop_fids_async: one device allocation for the
-// result and cap rows, async(d_rows, d_res), the result read back, then the rows when they are whole. must_fit: rows
-// that are not whole (fits == 0, or an overflow) are BCW_E_CAPACITY; otherwise they are the caller's to read.
+// result and cap rows (carve_usage), async(d_rows, d_res), the result read back, then the rows when they are whole.
+// must_fit: rows that are not whole (fits == 0, or an overflow) are BCW_E_CAPACITY; otherwise they are the caller's to
+// read.
 template <class Async>
 int ix_usage_sync(bcw_index* x, bcw_fid_usage* h_rows, uint32_t cap, bcw_usage_result* h_res, bool must_fit,
                   Async&& async) {
@@ -1570,20 +1532,17 @@ int ix_usage_sync(bcw_index* x, bcw_fid_usage* h_rows, uint32_t cap, bcw_usage_r
   DeviceGuard dg(c->device);
   if (!dg.ok) return BCW_E_HIP;
   DevBuf<> mem;
-  if (!mem.alloc(sizeof(bcw_usage_result) + (uint64_t)cap * sizeof(bcw_fid_usage))) return BCW_E_NOMEM;
-  bcw_usage_result* d_res = static_cast<bcw_usage_result*>(mem.get());
-  bcw_fid_usage* d_rows = cap ? reinterpret_cast<bcw_fid_usage*>(d_res + 1) : nullptr;
-  int rc = async(d_rows, d_res);
+  UsageLayout L;
+  int rc = carve_alloc(mem, [&](Carver& cv) { L = carve_usage(cv, cap); });
+  if (rc != BCW_OK) return rc;
+  rc = async(L.rows, L.res);
   if (rc == BCW_OK &&
-      (hipMemcpyAsync(h_res, d_res, sizeof *h_res, hipMemcpyDeviceToHost, c->cur) != hipSuccess ||
-       hipStreamSynchronize(c->cur) != hipSuccess))
+      (!copy_down(h_res, L.res, sizeof *h_res, c->cur) || hipStreamSynchronize(c->cur) != hipSuccess))
     rc = BCW_E_HIP;
   const bool whole = rc == BCW_OK && h_res->fits && !h_res->overflow;
   if (rc == BCW_OK && !whole && must_fit) rc = BCW_E_CAPACITY;
-  if (whole && h_res->n_fids &&
-      (hipMemcpyAsync(h_rows, d_rows, h_res->n_fids * sizeof(bcw_fid_usage), hipMemcpyDeviceToHost, c->cur) !=
-           hipSuccess ||
-       hipStreamSynchronize(c->cur) != hipSuccess))
+  if (whole && (!copy_down(h_rows, L.rows, h_res->n_fids * sizeof(bcw_fid_usage), c->cur) ||
+                hipStreamSynchronize(c->cur) != hipSuccess))
     rc = BCW_E_HIP;
   (void)hipStreamSynchronize(c->cur);  // before mem goes
   return rc;
@@ -1593,22 +1552,21 @@ int ix_usage_sync(bcw_index* x, bcw_fid_usage* h_rows, uint32_t cap, bcw_usage_r
 
 namespace bcw {
 int ix_launch_verify_select(bcw_index* x, VerifySelect& v, hipStream_t st) {
-  constexpr uint64_t kHead = vfy::V_NUM * sizeof(uint64_t);
-  if (x->cap > x->vfy_q_cap || !x->vfy_q) {
-    if (!x->vfy_q.reserve(kHead + x->cap * sizeof(vfy::Item), st)) {
-      x->vfy_q_cap = 0;
-      return BCW_E_NOMEM;
-    }
-    x->vfy_q_cap = x->cap;
-  }
-  v.cnt = static_cast<unsigned long long*>(x->vfy_q.get());
-  v.queue = v.cnt + vfy::V_NUM;
-  v.queue_cap = x->vfy_q_cap;
-  v.arena = x->arena;
-  if (hipMemsetAsync(v.cnt, 0, kHead, st) != hipSuccess) return BCW_E_HIP;
+  // grow-only: a table that shrank since keeps the queue, and the capacity, of the largest one
+  const uint64_t cap = std::max(x->cap, x->vfy_q_cap);
+  VfyQueueLayout Q;
+  const auto layout = [&](Carver& cv) { Q = carve_vfy_queue(cv, vfy::V_NUM, cap, sizeof(vfy::Item)); };
+  const int rc = carve_reserve(x->vfy_q, st, layout);
+  x->vfy_q_cap = rc == BCW_OK ? cap : 0;
+  if (rc != BCW_OK) return rc;
+  v.cnt = Q.cnt;
+  v.queue = Q.queue;
+  v.queue_cap = cap;
+  v.arena = x->arena.get();
+  if (hipMemsetAsync(v.cnt, 0, vfy::V_NUM * sizeof *v.cnt, st) != hipSuccess) return BCW_E_HIP;
   const vfy::Sink S{v.out, v.cnt, v.arena};
   return ix_usage_pass(x, K_VFY_SELECT, st, [&](uint32_t grid) {
-    k_ix_vfy_select<<<grid, usage::kThreads, 0, st>>>(x->slots, x->cap, v.wals, v.n_wals, S,
+    k_ix_vfy_select<<<grid, usage::kThreads, 0, st>>>(x->slots.get(), x->cap, v.wals, v.n_wals, S,
                                                       static_cast<vfy::Item*>(v.queue), v.queue_cap, v.scratch);
   });
 }
@@ -1634,13 +1592,14 @@ int ix_put_batch(bcw_index* x, const PutIx& p) {
     ix_batch(x, s, p.n, nullptr, 0, v, p.found, p.free_fid, p.free_bytes);
     if (p.found) {
       const uint32_t grid = (uint32_t)((p.n + 255) / 256);
-      uint64_t* link = x->op_kref.get();  // free again once k_ix_claim has run
-      k_put_link<<<grid, 256, 0, st>>>(x->cnt, x->slots, x->op_slot.get(), link);
-      k_put_stat<<<grid, 256, 0, st>>>(s, x->cnt, x->slots, x->op_slot.get(), link, p.found, p.free_fid, p.free_bytes);
-      k_put_unlink<<<grid, 256, 0, st>>>(x->cnt, x->slots, x->op_slot.get());
+      uint64_t* link = x->op.kref;  // free again once k_ix_claim has run
+      k_put_link<<<grid, 256, 0, st>>>(x->cnt.get(), x->slots.get(), x->op.slot, link);
+      k_put_stat<<<grid, 256, 0, st>>>(s, x->cnt.get(), x->slots.get(), x->op.slot, link, p.found, p.free_fid,
+                                       p.free_bytes);
+      k_put_unlink<<<grid, 256, 0, st>>>(x->cnt.get(), x->slots.get(), x->op.slot);
     }
   }
-  if (p.idx_err) k_put_idx_err<<<1, 1, 0, st>>>(x->cnt, p.idx_err);
+  if (p.idx_err) k_put_idx_err<<<1, 1, 0, st>>>(x->cnt.get(), p.idx_err);
   return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
 }
 
@@ -1654,21 +1613,20 @@ int ix_export(bcw_index* x, const uint64_t* h_fids, uint64_t n_fids, IxSink& sin
   fids.erase(std::unique(fids.begin(), fids.end()), fids.end());
   if (fids.size() > 0xffffffffull) return BCW_E_INVAL;
   const uint32_t nf = (uint32_t)fids.size();
-  const uint64_t fb = (8 * (uint64_t)nf + 15) & ~15ull, nblk = (x->cap + 255) / 256;
-  // staging: fids | per-block entry counts | per-block key bytes (then their exclusive prefixes) | outputs
-  int rc = ix_stage(x, fb + nblk * 16 + 64);
+  const uint64_t nblk = (x->cap + 255) / 256;
+  // staging (carve_ix_export): fids | per-block entry counts | per-block key bytes (then their exclusive prefixes) |
+  // outputs
+  IxExportLayout L;
+  const auto stage = [&](uint64_t tn, uint64_t tb) {
+    return carve_reserve(x->stage, st, [&](Carver& cv) { L = carve_ix_export(cv, nf, nblk, tn, tb); });
+  };
+  int rc = stage(0, 0);
   if (rc != BCW_OK) return rc;
-  uint64_t* d_fids = (uint64_t*)x->stage.get();
-  uint64_t* blk_n = (uint64_t*)((uint8_t*)x->stage.get() + fb);
-  uint64_t* blk_b = blk_n + nblk;
-  if (nf && hipMemcpyAsync(d_fids, fids.data(), 8 * (uint64_t)nf, hipMemcpyHostToDevice, st) != hipSuccess)
-    return BCW_E_HIP;
-  k_ix_count<<<(uint32_t)nblk, 256, 0, st>>>(x->slots, x->cap, x->arena, d_fids, nf, blk_n, blk_b);
+  if (!copy_up(L.fids, fids.data(), 8 * (uint64_t)nf, st)) return BCW_E_HIP;
+  k_ix_count<<<(uint32_t)nblk, 256, 0, st>>>(x->slots.get(), x->cap, x->arena.get(), L.fids, nf, L.blk_n, L.blk_b);
   std::vector<uint64_t> hn(nblk), hb(nblk);
-  if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(hn.data(), blk_n, nblk * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(hb.data(), blk_b, nblk * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
+  if (hipGetLastError() != hipSuccess || !copy_down(hn.data(), L.blk_n, nblk * 8, st) ||
+      !copy_down(hb.data(), L.blk_b, nblk * 8, st) || hipStreamSynchronize(st) != hipSuccess)
     return BCW_E_HIP;
   uint64_t tn = 0, tb = 0;
   for (uint64_t b = 0; b < nblk; ++b) {
@@ -1682,35 +1640,20 @@ int ix_export(bcw_index* x, const uint64_t* h_fids, uint64_t n_fids, IxSink& sin
   *key_bytes = tb;
   rc = sink.room(tn, tb);
   if (rc != BCW_OK || tn == 0) return rc;
-  const uint64_t tbp = (tb + 15) & ~15ull;
-  rc = ix_stage(x, fb + nblk * 16 + tbp + 8 * (tn + 1) + 24 * tn + 64);  // a regrow drops the contents
+  rc = stage(tn, tb);  // a regrow drops the contents: the fids go up again, with the prefixes
   if (rc != BCW_OK) return rc;
-  d_fids = (uint64_t*)x->stage.get();
-  uint64_t* pn = (uint64_t*)((uint8_t*)x->stage.get() + fb);
-  uint64_t* pb = pn + nblk;
-  uint8_t* keys = (uint8_t*)(pb + nblk);
-  uint64_t* koff = (uint64_t*)(keys + tbp);
-  uint64_t* fid = koff + tn + 1;
-  uint64_t* off = fid + tn;
-  uint64_t* size = off + tn;
-  bool ok = (!nf || hipMemcpyAsync(d_fids, fids.data(), 8 * (uint64_t)nf, hipMemcpyHostToDevice, st) == hipSuccess) &&
-            hipMemcpyAsync(pn, hn.data(), nblk * 8, hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(pb, hb.data(), nblk * 8, hipMemcpyHostToDevice, st) == hipSuccess;
+  bool ok = copy_up(L.fids, fids.data(), 8 * (uint64_t)nf, st) && copy_up(L.blk_n, hn.data(), nblk * 8, st) &&
+            copy_up(L.blk_b, hb.data(), nblk * 8, st);
   if (ok)
-    k_ix_export<<<(uint32_t)nblk, 256, 0, st>>>(x->slots, x->cap, x->arena, d_fids, nf, pn, pb, keys, koff, fid, off,
-                                                  size);
-  ok = ok && hipGetLastError() == hipSuccess &&
-       hipMemcpyAsync(sink.keys, keys, tb, hipMemcpyDeviceToHost, st) == hipSuccess &&
-       hipMemcpyAsync(sink.koff, koff, 8 * (tn + 1), hipMemcpyDeviceToHost, st) == hipSuccess &&
-       hipMemcpyAsync(sink.fid, fid, 8 * tn, hipMemcpyDeviceToHost, st) == hipSuccess &&
-       hipMemcpyAsync(sink.off, off, 8 * tn, hipMemcpyDeviceToHost, st) == hipSuccess &&
-       hipMemcpyAsync(sink.size, size, 8 * tn, hipMemcpyDeviceToHost, st) == hipSuccess &&
+    k_ix_export<<<(uint32_t)nblk, 256, 0, st>>>(x->slots.get(), x->cap, x->arena.get(), L.fids, nf, L.blk_n, L.blk_b,
+                                                  L.k.keys, L.k.key_off, L.fid, L.off, L.size);
+  ok = ok && hipGetLastError() == hipSuccess && copy_down(sink.keys, L.k.keys, tb, st) &&
+       copy_down(sink.koff, L.k.key_off, 8 * (tn + 1), st) && copy_down(sink.fid, L.fid, 8 * tn, st) &&
+       copy_down(sink.off, L.off, 8 * tn, st) && copy_down(sink.size, L.size, 8 * tn, st) &&
        hipStreamSynchronize(st) == hipSuccess;
   return ok ? BCW_OK : BCW_E_HIP;
 }
-}  // namespace bcw
 
-namespace bcw {
 int ix_filter_on(bcw_index* x, bcw_ctx* c, const uint8_t* d_seg, const bcw_decode_params* p,
                  const bcw_record_table* d_table, const bcw_decode_result* d_result, uint64_t src_fid, uint8_t* d_keep,
                  uint64_t* d_cnt, bcw_index_result* d_out) {
@@ -1736,19 +1679,17 @@ int ix_rule_commit(bcw_index* x) {
   if (!x->rules.mask) return BCW_OK;
   DeviceGuard dg(x->ctx->device);
   if (!dg.ok) return BCW_E_HIP;
-  k_ix_rule_commit<<<1, 1, 0, x->ctx->cur>>>(x->d_rule_cnt);
+  k_ix_rule_commit<<<1, 1, 0, x->ctx->cur>>>(x->d_rule_cnt.get());
   return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
 }
-}  // namespace bcw
 
-namespace bcw {
 // bcw_compact_filter_async, with the rows the rules drop counted apart, for ix_rule_commit
 int ix_filter_pending(bcw_index* x, const uint8_t* d_seg, const bcw_decode_params* p, const bcw_record_table* d_table,
                       const bcw_decode_result* d_result, uint64_t src_fid, uint8_t* d_keep, bcw_index_result* d_out) {
   if (!x) return BCW_E_INVAL;
   const bool apart = x->rules.mask != 0;  // rule counters [3, 6): the compaction in progress
-  return ix_filter(x, x->ctx, d_seg, p, d_table, d_result, src_fid, d_keep, x->cnt, x->d_rule_cnt + (apart ? 3 : 0),
-                   apart, d_out);
+  return ix_filter(x, x->ctx, d_seg, p, d_table, d_result, src_fid, d_keep, x->cnt.get(),
+                   x->d_rule_cnt.get() + (apart ? 3 : 0), apart, d_out);
 }
 }  // namespace bcw
 
@@ -1762,27 +1703,22 @@ int bcw_index_create(bcw_ctx* c, uint64_t keys, uint64_t arena_bytes, bcw_index*
   bcw_index* x = new (std::nothrow) bcw_index();
   if (!x) return BCW_E_NOMEM;
   x->ctx = c;
-  if (hipMalloc(&x->cnt, C_NUM * sizeof(uint64_t)) != hipSuccess ||
-      hipMalloc(&x->d_res, sizeof(bcw_index_result)) != hipSuccess ||
-      hipMemsetAsync(x->cnt, 0, C_NUM * sizeof(uint64_t), c->cur) != hipSuccess) {
-    bcw_index_destroy(x);
-    return BCW_E_NOMEM;
-  }
-  const int rc = ix_grow(x, std::max<uint64_t>(keys, 1024), std::max<uint64_t>(arena_bytes, 1 << 20));
-  if (rc != BCW_OK) { bcw_index_destroy(x); return rc; }
-  *out = x;
-  return BCW_OK;
+  const bool ok = x->cnt.alloc(C_NUM * sizeof(uint64_t)) &&
+                  hipMemsetAsync(x->cnt.get(), 0, C_NUM * sizeof(uint64_t), c->cur) == hipSuccess;
+  const int rc =
+      ok ? ix_grow(x, std::max<uint64_t>(keys, 1024), std::max<uint64_t>(arena_bytes, 1 << 20)) : BCW_E_NOMEM;
+  if (rc != BCW_OK) bcw_index_destroy(x);  // whatever it holds by now goes with it
+  else *out = x;
+  return rc;
 }
 
 int bcw_index_destroy(bcw_index* x) {
   if (!x) return BCW_E_INVAL;
   DeviceGuard dg(x->ctx->device);
   (void)hipStreamSynchronize(x->ctx->cur);
-  void* ptrs[] = {x->slots, x->arena, x->cnt, x->d_res, x->d_rule_tab, x->d_rule_cnt};
-  for (void* q : ptrs) (void)hipFree(q);
   if (x->drop_h) (void)hipHostFree(x->drop_h);
   if (x->drop_ev) (void)hipEventDestroy(x->drop_ev);
-  delete x;
+  delete x;  // the device buffers go here (DevBuf), on the index's device: inside dg's scope
   return BCW_OK;
 }
 
@@ -1808,7 +1744,7 @@ int bcw_index_stats(bcw_index* x, bcw_index_info* out) {
   out->slots_used = c[C_SLOTS];
   out->slot_capacity = x->cap;
   out->arena_used = c[C_ARENA];
-  out->arena_capacity = x->arena_cap;
+  out->arena_capacity = x->arena.bytes();
   out->overflow = c[C_OVERFLOW];
   out->limited = x->limited;
   out->evicted = c[C_EVICTED];
@@ -1830,13 +1766,13 @@ int bcw_index_compact(bcw_index* x, int shrink) {
   DeviceGuard dg(x->ctx->device);
   if (!dg.ok) return BCW_E_HIP;
   hipStream_t st = x->ctx->cur;
-  uint64_t ncap = x->cap, narena = x->arena_cap;
-  if (shrink && hipMemsetAsync(x->cnt + C_R_ARENA, 0, sizeof(uint64_t), st) != hipSuccess) return BCW_E_HIP;
+  uint64_t ncap = x->cap, narena = x->arena.bytes();
+  if (shrink && hipMemsetAsync(x->cnt.get() + C_R_ARENA, 0, sizeof(uint64_t), st) != hipSuccess) return BCW_E_HIP;
   if (shrink) {
     hipEvent_t ev = nullptr;
     x->ctx->prof.begin(K_IX_LIVE_BYTES, st, ev);
-    k_ix_live_bytes<<<(uint32_t)((x->cap + 255) / 256), 256, 0, st>>>(x->slots, x->cap, x->arena, x->arena_cap,
-                                                                      x->cnt + C_R_ARENA);
+    k_ix_live_bytes<<<(uint32_t)((x->cap + 255) / 256), 256, 0, st>>>(x->slots.get(), x->cap, x->arena.get(),
+                                                                      x->arena.bytes(), x->cnt.get() + C_R_ARENA);
     x->ctx->prof.end(K_IX_LIVE_BYTES, st, ev);
   }
   uint64_t c[C_NUM];
@@ -1866,29 +1802,20 @@ int bcw_index_apply_stat(bcw_index* x, uint64_t n, const uint8_t* h_keys, const 
   const uint64_t arena_b = 16 * n + (h_key_off[n] - h_key_off[0]) + 15 * n;
   rc = ix_room(x, n, arena_b);
   if (rc != BCW_OK) return rc;
-  // staging: keys | key offsets (rebased) | fid | off | size | WriteStat (fid, size) | ops | found
-  FlatStage f;
-  rc = stage_flat_keys(x, n, h_keys, h_key_off, 40 * n + 2 * n, &f);
+  IxApplyLayout L;
+  std::vector<uint64_t> koff;
+  rc = stage_flat_keys(x, n, h_keys, h_key_off, carve_ix_apply, &L, &koff);
   if (rc != BCW_OK) return rc;
-  uint64_t* d_fid = (uint64_t*)f.rest;
-  uint64_t* d_off = d_fid + n;
-  uint64_t* d_size = d_off + n;
-  uint64_t* d_ofid = d_size + n;
-  uint64_t* d_osize = d_ofid + n;
-  uint8_t* d_ops = (uint8_t*)(d_osize + n);
-  uint8_t* d_found = d_ops + n;
   hipStream_t st = x->ctx->cur;
-  bool ok = hipMemcpyAsync(d_fid, h_fid, 8 * n, hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(d_off, h_off, 8 * n, hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(d_size, h_size, 8 * n, hipMemcpyHostToDevice, st) == hipSuccess &&
-            hipMemcpyAsync(d_ops, h_ops, n, hipMemcpyHostToDevice, st) == hipSuccess;
+  bool ok = copy_up(L.fid, h_fid, 8 * n, st) && copy_up(L.off, h_off, 8 * n, st) &&
+            copy_up(L.size, h_size, 8 * n, st) && copy_up(L.ops, h_ops, n, st);
   if (!ok) return BCW_E_HIP;
-  OpVals v{d_ops, d_fid, d_off, d_size, 0, 0};
-  ix_batch(x, f.src, n, nullptr, 0, v, stat ? d_found : nullptr, d_ofid, d_osize);
+  OpVals v{L.ops, L.fid, L.off, L.size, 0, 0};
+  ix_batch(x, flat_src(L.k.keys, L.k.key_off, koff[n]), n, nullptr, 0, v, stat ? L.found : nullptr, L.free_fid,
+           L.free_bytes);
   if (stat)
-    ok = hipMemcpyAsync(h_found, d_found, n, hipMemcpyDeviceToHost, st) == hipSuccess &&
-         hipMemcpyAsync(h_free_fid, d_ofid, 8 * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
-         hipMemcpyAsync(h_free_bytes, d_osize, 8 * n, hipMemcpyDeviceToHost, st) == hipSuccess;
+    ok = copy_down(h_found, L.found, n, st) && copy_down(h_free_fid, L.free_fid, 8 * n, st) &&
+         copy_down(h_free_bytes, L.free_bytes, 8 * n, st);
   if (!ok || hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return BCW_E_HIP;
   if (stat) {
     // the device reported, per op, the value the key held before the batch; an op preceded by another op on the
@@ -1928,8 +1855,8 @@ int bcw_index_clear(bcw_index* x) {
   DeviceGuard dg(x->ctx->device);
   if (!dg.ok) return BCW_E_HIP;
   hipStream_t st = x->ctx->cur;
-  if (hipMemsetAsync(x->slots, 0, x->cap * sizeof(Slot), st) != hipSuccess ||
-      hipMemsetAsync(x->cnt, 0, C_NUM * sizeof(uint64_t), st) != hipSuccess)
+  if (hipMemsetAsync(x->slots.get(), 0, x->cap * sizeof(Slot), st) != hipSuccess ||
+      hipMemsetAsync(x->cnt.get(), 0, C_NUM * sizeof(uint64_t), st) != hipSuccess)
     return BCW_E_HIP;
   x->slots_ub = 0;
   x->arena_ub = 0;
@@ -1944,23 +1871,16 @@ int bcw_index_get(bcw_index* x, uint64_t n, const uint8_t* h_keys, const uint64_
   if (rc != BCW_OK) return rc;
   DeviceGuard dg(x->ctx->device);
   if (!dg.ok) return BCW_E_HIP;
-  // staging: keys | key offsets (rebased) | fid | off | size | status
-  FlatStage f;
-  rc = stage_flat_keys(x, n, h_keys, h_key_off, 24 * n + n, &f);
+  IxGetLayout L;
+  std::vector<uint64_t> koff;
+  rc = stage_flat_keys(x, n, h_keys, h_key_off, carve_ix_get, &L, &koff);
   if (rc != BCW_OK) return rc;
-  uint64_t* d_fid = (uint64_t*)f.rest;
-  uint64_t* d_off = d_fid + n;
-  uint64_t* d_size = d_off + n;
-  uint8_t* d_st = (uint8_t*)(d_size + n);
   hipStream_t st = x->ctx->cur;
-  k_ix_get<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(f.src, n, x->slots, x->cap - 1, x->arena, d_fid, d_off,
-                                                         d_size, d_st);
-  const bool ok = hipGetLastError() == hipSuccess &&
-       hipMemcpyAsync(h_fid, d_fid, 8 * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
-       hipMemcpyAsync(h_off, d_off, 8 * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
-       hipMemcpyAsync(h_size, d_size, 8 * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
-       hipMemcpyAsync(h_status, d_st, n, hipMemcpyDeviceToHost, st) == hipSuccess &&
-       hipStreamSynchronize(st) == hipSuccess;
+  k_ix_get<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(flat_src(L.k.keys, L.k.key_off, koff[n]), n, x->slots.get(),
+                                                         x->cap - 1, x->arena.get(), L.fid, L.off, L.size, L.status);
+  const bool ok = hipGetLastError() == hipSuccess && copy_down(h_fid, L.fid, 8 * n, st) &&
+                  copy_down(h_off, L.off, 8 * n, st) && copy_down(h_size, L.size, 8 * n, st) &&
+                  copy_down(h_status, L.status, n, st) && hipStreamSynchronize(st) == hipSuccess;
   return ok ? BCW_OK : BCW_E_HIP;
 }
 
@@ -1981,9 +1901,9 @@ int bcw_index_put_decoded_async(bcw_index* x, const uint8_t* d_seg, const bcw_de
   // read back instead (one small launch and a sync): only keys new to the index take arena space, so an
   // index rebuilt over keys it already holds does not grow.
   uint64_t arena_b = p->seg_len + 32 * rows;
-  if (x->arena_ub + arena_b > x->arena_cap && rows) {
-    if (hipMemsetAsync(x->cnt + C_NEED, 0, sizeof(uint64_t), c->cur) != hipSuccess) return BCW_E_HIP;
-    k_ix_need<<<(uint32_t)((rows + 255) / 256), 256, 0, c->cur>>>(s, rows, d_result, c->frag_gen, x->cnt);
+  if (x->arena_ub + arena_b > x->arena.bytes() && rows) {
+    if (hipMemsetAsync(x->cnt.get() + C_NEED, 0, sizeof(uint64_t), c->cur) != hipSuccess) return BCW_E_HIP;
+    k_ix_need<<<(uint32_t)((rows + 255) / 256), 256, 0, c->cur>>>(s, rows, d_result, c->frag_gen, x->cnt.get());
     uint64_t cc[C_NUM];
     int rc0 = ix_sync_counters(x, cc);
     if (rc0 != BCW_OK) return rc0;
@@ -1995,7 +1915,7 @@ int bcw_index_put_decoded_async(bcw_index* x, const uint8_t* d_seg, const bcw_de
   if (rc != BCW_OK) return rc;
   OpVals v{nullptr, nullptr, nullptr, nullptr, fid, use_record_fid};
   ix_batch(x, s, rows, d_result, c->frag_gen, v);
-  if (d_out) k_ix_result<<<1, 1, 0, c->cur>>>(x->cnt, d_out);
+  if (d_out) k_ix_result<<<1, 1, 0, c->cur>>>(x->cnt.get(), d_out);
   return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
 }
 
@@ -2003,7 +1923,8 @@ int bcw_compact_filter_async(bcw_index* x, const uint8_t* d_seg, const bcw_decod
                              const bcw_record_table* d_table, const bcw_decode_result* d_result, uint64_t src_fid,
                              uint8_t* d_keep, bcw_index_result* d_out) {
   if (!x) return BCW_E_INVAL;
-  return ix_filter(x, x->ctx, d_seg, p, d_table, d_result, src_fid, d_keep, x->cnt, x->d_rule_cnt, false, d_out);
+  return ix_filter(x, x->ctx, d_seg, p, d_table, d_result, src_fid, d_keep, x->cnt.get(), x->d_rule_cnt.get(), false,
+                   d_out);
 }
 
 int bcw_index_set_compact_rules(bcw_index* x, const bcw_compact_rules* r) {
@@ -2013,15 +1934,11 @@ int bcw_index_set_compact_rules(bcw_index* x, const bcw_compact_rules* r) {
   hipStream_t st = x->ctx->cur;
   const bool on = r && r->mask;
   if (on && !x->d_rule_tab) {
-    rules::PrefixTable* t = nullptr;
-    uint64_t* cnt = nullptr;
-    if (hipMalloc(&t, sizeof *t) != hipSuccess || hipMalloc(&cnt, 6 * sizeof(uint64_t)) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(t);
-      return BCW_E_NOMEM;
-    }
-    x->d_rule_tab = t;
-    x->d_rule_cnt = cnt;
+    DevBuf<rules::PrefixTable> t;
+    DevBuf<uint64_t> cnt;
+    if (!t.alloc(sizeof(rules::PrefixTable)) || !cnt.alloc(6 * sizeof(uint64_t))) return BCW_E_NOMEM;
+    x->d_rule_tab = std::move(t);
+    x->d_rule_cnt = std::move(cnt);
   }
   // the copy of the caller's arrays, made before anything of the index changes
   std::vector<uint8_t> bytes;
@@ -2035,9 +1952,10 @@ int bcw_index_set_compact_rules(bcw_index* x, const bcw_compact_rules* r) {
     }
     longest = rules::pack(*r, &tab);
     // ordered on the stream after the filters queued so far; the sync below keeps `tab` alive for the copy
-    if (hipMemcpyAsync(x->d_rule_tab, &tab, sizeof tab, hipMemcpyHostToDevice, st) != hipSuccess) return BCW_E_HIP;
+    if (hipMemcpyAsync(x->d_rule_tab.get(), &tab, sizeof tab, hipMemcpyHostToDevice, st) != hipSuccess)
+      return BCW_E_HIP;
   }
-  if (x->d_rule_cnt && hipMemsetAsync(x->d_rule_cnt, 0, 6 * sizeof(uint64_t), st) != hipSuccess) return BCW_E_HIP;
+  if (x->d_rule_cnt && hipMemsetAsync(x->d_rule_cnt.get(), 0, 6 * sizeof(uint64_t), st) != hipSuccess) return BCW_E_HIP;
   if (hipStreamSynchronize(st) != hipSuccess) return BCW_E_HIP;
   x->rule_bytes.swap(bytes);
   x->rule_off.swap(off);
@@ -2060,7 +1978,7 @@ int bcw_index_compact_rule_counts(bcw_index* x, uint64_t out[3]) {
   if (!dg.ok) return BCW_E_HIP;
   hipStream_t st = x->ctx->cur;
   uint64_t c[3] = {0, 0, 0};
-  if (x->d_rule_cnt && hipMemcpyAsync(c, x->d_rule_cnt, sizeof c, hipMemcpyDeviceToHost, st) != hipSuccess)
+  if (x->d_rule_cnt && hipMemcpyAsync(c, x->d_rule_cnt.get(), sizeof c, hipMemcpyDeviceToHost, st) != hipSuccess)
     return BCW_E_HIP;
   if (hipStreamSynchronize(st) != hipSuccess) return BCW_E_HIP;
   for (int r = 0; r < 3; ++r) out[r] = c[r] + x->rule_host[r];
@@ -2106,7 +2024,7 @@ int bcw_index_fid_usage_async(bcw_index* x, bcw_fid_usage* d_rows, uint32_t cap,
   const int rc = usage_begin(c, st, &scratch);
   if (rc != BCW_OK) return rc;
   const int rp = ix_usage_pass(x, K_USAGE_INDEX, st, [&](uint32_t grid) {
-    k_ix_usage<<<grid, usage::kThreads, 0, st>>>(x->slots, x->cap, scratch);
+    k_ix_usage<<<grid, usage::kThreads, 0, st>>>(x->slots.get(), x->cap, scratch);
   });
   return rp != BCW_OK ? rp : usage_finish(c, st, d_rows, cap, d_res, 1);
 }
@@ -2157,8 +2075,8 @@ int bcw_index_drop_fids_async(bcw_index* x, int mode, const uint64_t* h_fids, ui
   rc = usage_begin(c, st, &scratch);
   if (rc != BCW_OK) return rc;
   rc = ix_usage_pass(x, K_IX_DROP, st, [&](uint32_t grid) {
-    k_ix_drop<<<grid, usage::kThreads, (size_t)nf * sizeof(uint64_t), st>>>(x->slots, x->cap, x->drop_d.get(), nf, mode,
-                                                                           scratch, x->cnt);
+    k_ix_drop<<<grid, usage::kThreads, (size_t)nf * sizeof(uint64_t), st>>>(x->slots.get(), x->cap, x->drop_d.get(), nf,
+                                                                           mode, scratch, x->cnt.get());
   });
   return rc != BCW_OK ? rc : usage_finish(c, st, d_rows, cap, d_res, 1);
 }

@@ -578,28 +578,24 @@ int bcw_write_records(bcw_index* ix, const bcw_write_params* p, const bcw_write_
     off[n + 1 + i] = hb->val_off[i] - hb->val_off[0];
     off[2 * (n + 1) + i] = hb->meta_off[i] - hb->meta_off[0];
   }
-  auto up = [&](void* dst, const void* src, uint64_t nb) {
-    return nb == 0 || hipMemcpyAsync(dst, src, nb, hipMemcpyHostToDevice, st) == hipSuccess;
-  };
-  auto down = [&](void* dst, const void* src, uint64_t nb) {
-    return !dst || nb == 0 || hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToHost, st) == hipSuccess;
-  };
   bool ok = true;
   if (n)
-    ok = up(L.keys, kb ? hb->keys + hb->key_off[0] : nullptr, kb) &&
-         up(L.vals, vb ? hb->vals + hb->val_off[0] : nullptr, vb) &&
-         up(L.metas, mb ? hb->metas + hb->meta_off[0] : nullptr, mb) && up(L.etags, hb->etags, eb) &&
-         up(L.offs, off.data(), 3 * 8 * (n + 1)) && up(L.expire, hb->expire, 8 * n) && up(L.flags, hb->flags, n);
+    ok = copy_up(L.keys, kb ? hb->keys + hb->key_off[0] : nullptr, kb, st) &&
+         copy_up(L.vals, vb ? hb->vals + hb->val_off[0] : nullptr, vb, st) &&
+         copy_up(L.metas, mb ? hb->metas + hb->meta_off[0] : nullptr, mb, st) && copy_up(L.etags, hb->etags, eb, st) &&
+         copy_up(L.offs, off.data(), 3 * 8 * (n + 1), st) && copy_up(L.expire, hb->expire, 8 * n, st) &&
+         copy_up(L.flags, hb->flags, n, st);
   int rc = ok ? bcw_write_records_async(ix, p, &db, &d, L.res) : BCW_E_HIP;
   if (rc == BCW_OK) {
-    ok = down(h_result, L.res, sizeof(bcw_write_result)) && hipStreamSynchronize(st) == hipSuccess;
+    ok = copy_down(h_result, L.res, sizeof(bcw_write_result), st) && hipStreamSynchronize(st) == hipSuccess;
     rc = !ok ? BCW_E_HIP : h_result->fits ? BCW_OK : BCW_E_CAPACITY;
   }
   if (rc == BCW_OK && h_result->n_written) {
-    ok = down(ho->wal, d.wal, h_result->wal_need) && down(ho->rec_off, d.rec_off, 8 * n) &&
-         down(ho->rec_size, d.rec_size, 8 * n);
+    ok = copy_down(ho->wal, d.wal, h_result->wal_need, st) && copy_down(ho->rec_off, d.rec_off, 8 * n, st) &&
+         copy_down(ho->rec_size, d.rec_size, 8 * n, st);
     if (ok && stat)
-      ok = down(ho->found, d.found, n) && down(ho->free_fid, d.free_fid, 8 * n) && down(ho->free_bytes, d.free_bytes, 8 * n);
+      ok = copy_down(ho->found, d.found, n, st) && copy_down(ho->free_fid, d.free_fid, 8 * n, st) &&
+           copy_down(ho->free_bytes, d.free_bytes, 8 * n, st);
     if (!ok) rc = BCW_E_HIP;
   }
   if (hipStreamSynchronize(st) != hipSuccess && rc == BCW_OK) rc = BCW_E_HIP;  // before mem goes

@@ -208,17 +208,14 @@ int bcw_index_verify(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p, con
   if (!h.bad_cap) d.bad = nullptr;
   if (!h.keys_cap) d.keys = nullptr;
   if (!h.rows_cap) d.rows = nullptr;
-  auto down = [&](void* dst, const void* src, uint64_t b) {
-    return b == 0 || hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, st) == hipSuccess;
-  };
   int rc = bcw_index_verify_async(ix, ws, p, &d, d_res);
   if (rc == BCW_OK)
-    rc = down(h_res, d_res, sizeof *h_res) && hipStreamSynchronize(st) == hipSuccess ? BCW_OK : BCW_E_HIP;
+    rc = copy_down(h_res, d_res, sizeof *h_res, st) && hipStreamSynchronize(st) == hipSuccess ? BCW_OK : BCW_E_HIP;
   if (rc == BCW_OK && !h_res->fits) rc = BCW_E_CAPACITY;
   if (rc == BCW_OK) {
-    const bool ok = down(h.bad, d.bad, h_res->n_bad * sizeof(bcw_verify_bad)) &&
-                    down(h.keys, d.keys, h_res->bad_key_bytes) &&
-                    down(h.rows, d.rows, h_res->per_fid.n_fids * sizeof(bcw_fid_usage)) &&
+    const bool ok = copy_down(h.bad, d.bad, h_res->n_bad * sizeof(bcw_verify_bad), st) &&
+                    copy_down(h.keys, d.keys, h_res->bad_key_bytes, st) &&
+                    copy_down(h.rows, d.rows, h_res->per_fid.n_fids * sizeof(bcw_fid_usage), st) &&
                     hipStreamSynchronize(st) == hipSuccess;
     if (!ok) rc = BCW_E_HIP;
   }

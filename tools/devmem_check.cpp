@@ -1,14 +1,19 @@
 // devmem_check.cpp -- the host's device-memory types, column list and layouts (csrc/bcw_devmem.h) as a
 // stand-alone program. No device, no library: the few HIP names the header uses are stand-ins defined here
 // (BCW_DEVMEM_NO_HIP), a "device allocation" is host memory, and the stand-ins keep a log of what was called.
-//   the carver: for the six layouts (fragments, read, get, put, encode outputs, the record table) at n = 0, 1, 2, 255,
-//   256, 257, with and without the optional table, byte counts 0, 1, 15, 16, 17 -- the measured total is where the
-//   carve pass ends, every pointer is aligned to its element (16 B for payload, hint WAL and the result structs), the
-//   arrays do not overlap and stay inside the allocation; a take past the end is refused, for good;
+//   the carver: for the twelve layouts (fragments, read, get, put, encode outputs, the record table; the index's flat
+//   keys, apply, get, export in both phases, usage rows, scrub queue) at n = 0, 1, 2, 255, 256, 257, with and without
+//   the optional parts, byte counts 0, 1, 15, 16, 17 -- the measured total is where the carve pass ends, every pointer
+//   is aligned to its element (16 B for payload, hint WAL and the result structs), the arrays do not overlap and stay
+//   inside the allocation; a take past the end is refused, for good; get, index apply and index get begin with the
+//   flat-key layout, export's second phase with its first;
 //   the column list: the required-column sets of decode / encode and of read / get, the carve with and without the
 //   hint columns, the copy that skips columns either side lacks;
-//   the owner: reserve's order (synchronise, free, allocate), its fast path without a call, null / 0 after a failed
-//   allocation, one free per allocation across moves and destruction.
+//   the owner: reserve's order (synchronise, free, allocate), its fast path without a call, null / 0 and no error left
+//   behind after a failed allocation, one free per allocation across moves and destruction; adopt's order (the new
+//   allocation, synchronise, free of the old one), and a pair whose second allocation fails leaks nothing and leaves
+//   what is held alone; carve_reserve keeps a buffer that is large enough without a call and refuses a layout whose
+//   carve pass asks for more than its measure pass, however large the buffer.
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude -Ibitcaskdb_amd/csrc \
 //       tools/devmem_check.cpp -o /tmp/devmem_check && /tmp/devmem_check
 #include <algorithm>
@@ -24,12 +29,14 @@
 typedef int hipError_t;
 typedef void* hipStream_t;
 constexpr hipError_t hipSuccess = 0;
-enum hipMemcpyKind { hipMemcpyDeviceToHost = 2 };
+enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2 };
 static std::string g_log;         // 'S' synchronise, 'F' free of a live pointer, 'M' allocate, 'C' copy
 static int g_live = 0;            // allocations not yet freed
 static bool g_fail_next = false;  // the next allocation fails
+static hipError_t g_err = hipSuccess;  // the error a failed call leaves on the thread until it is read
+static hipError_t hipGetLastError() { return std::exchange(g_err, hipSuccess); }
 static hipError_t hipMalloc(void** p, size_t n) {
-  if (g_fail_next) { g_fail_next = false; *p = reinterpret_cast<void*>(0x1); return 2; }  // garbage, as a failed call may leave
+  if (g_fail_next) { g_fail_next = false; *p = reinterpret_cast<void*>(0x1); return g_err = 2; }  // garbage, as a failed call may leave
   *p = std::aligned_alloc(256, (n + 255) / 256 * 256 + 256);
   ++g_live;
   g_log += 'M';
@@ -101,10 +108,68 @@ static bool both_passes(Layout layout) {
   return ok;
 }
 
+// k is where the flat-key layout of (key_bytes, n) puts it when that layout begins the allocation (k.keys is the base)
+static bool flat_prefix(const Carver& cv, const FlatKeys& k, uint64_t key_bytes, uint64_t n) {
+  if (!k.keys || !cv.ok()) return true;  // the measuring pass, or a carve that was refused
+  Carver ref(k.keys, ~0ull);
+  const FlatKeys f = carve_flat_keys(ref, key_bytes, n);
+  return f.keys == k.keys && f.key_off == k.key_off;
+}
+
 int main() {
   const uint64_t kN[] = {0, 1, 2, 255, 256, 257}, kBytes[] = {0, 1, 15, 16, 17};
   unsigned long long layouts = 0;
   for (uint64_t n : kN) {
+    // the index's layouts: usage rows (cap = n, 0 included), the scrub queue (24 counter words, 48-byte items)
+    CHECK(both_passes([&](Carver& cv, Spans& sp) {
+      const UsageLayout L = carve_usage(cv, n);
+      sp.add(L.res, 1, 16);
+      if (n) sp.add(L.rows, n, 16);
+      if (L.res && cv.ok()) g_bad |= (L.rows != nullptr) != (n != 0);
+    }));
+    CHECK(both_passes([&](Carver& cv, Spans& sp) {
+      const VfyQueueLayout L = carve_vfy_queue(cv, 24, n, 48);
+      sp.add(L.cnt, 24, 16); sp.add(static_cast<const uint8_t*>(L.queue), n * 48, 16);
+    }));
+    layouts += 2;
+    for (uint64_t a : kBytes) {
+      CHECK(both_passes([&](Carver& cv, Spans& sp) {
+        const FlatKeys k = carve_flat_keys(cv, a, n);
+        sp.add(k.keys, a, 16); sp.add(k.key_off, n + 1);
+      }));
+      CHECK(both_passes([&](Carver& cv, Spans& sp) {
+        const IxApplyLayout L = carve_ix_apply(cv, a, n);
+        sp.add(L.k.keys, a, 16); sp.add(L.k.key_off, n + 1); sp.add(L.fid, n); sp.add(L.off, n); sp.add(L.size, n);
+        sp.add(L.free_fid, n); sp.add(L.free_bytes, n); sp.add(L.ops, n); sp.add(L.found, n);
+        g_bad |= !flat_prefix(cv, L.k, a, n);
+      }));
+      CHECK(both_passes([&](Carver& cv, Spans& sp) {
+        const IxGetLayout L = carve_ix_get(cv, a, n);
+        sp.add(L.k.keys, a, 16); sp.add(L.k.key_off, n + 1); sp.add(L.fid, n); sp.add(L.off, n); sp.add(L.size, n);
+        sp.add(L.status, n);
+        g_bad |= !flat_prefix(cv, L.k, a, n);
+      }));
+      layouts += 3;
+      // the export: nf selected fids (none included), n blocks; phase one, and phase two with n entries of a key
+      // bytes, whose first part lies where phase one put it
+      for (uint64_t nf : {0, 1, 3})
+        for (bool two : {false, true}) {
+          if (two && !n) continue;  // no entries: the export ends after phase one
+          CHECK(both_passes([&](Carver& cv, Spans& sp) {
+            const IxExportLayout L = carve_ix_export(cv, nf, n, two ? n : 0, two ? a : 0);
+            sp.add(L.fids, nf, 16); sp.add(L.blk_n, n, 16); sp.add(L.blk_b, n);
+            if (two) {
+              sp.add(L.k.keys, a, 16); sp.add(L.k.key_off, n + 1); sp.add(L.fid, n); sp.add(L.off, n); sp.add(L.size, n);
+            }
+            if (!L.fids || !cv.ok()) return;  // the measuring pass, or a carve that was refused
+            g_bad |= two != (L.k.keys != nullptr) || two != (L.k.key_off != nullptr) || two != (L.size != nullptr);
+            Carver ref(L.fids, ~0ull);
+            const IxExportLayout P = carve_ix_export(ref, nf, n, 0, 0);
+            g_bad |= P.fids != L.fids || P.blk_n != L.blk_n || P.blk_b != L.blk_b;
+          }));
+          ++layouts;
+        }
+    }
     CHECK(both_passes([&](Carver& cv, Spans& sp) {
       const bcw_frag_table d = carve_frags(cv, n);
       sp.add(d.data_off, n); sp.add(d.len, n); sp.add(d.stored_crc, n); sp.add(d.type, n); sp.add(d.crc_ok, n);
@@ -128,11 +193,12 @@ int main() {
           }));
           CHECK(both_passes([&](Carver& cv, Spans& sp) {
             const GetLayout L = carve_get(cv, a, b, n, tab);
-            sp.add(L.keys, a, 16); sp.add(L.out.payload, b, 16); sp.add(L.key_off, n + 1); sp.add(L.out.fid, n);
+            sp.add(L.k.keys, a, 16); sp.add(L.out.payload, b, 16); sp.add(L.k.key_off, n + 1); sp.add(L.out.fid, n);
             sp.add(L.out.off, n); sp.add(L.out.size, n); sp.add(L.out.pay_off, n); sp.add(L.out.get_status, n);
             sp.add(L.out.rd_status, n); sp.add(L.res, 1, 16);
             if (tab) sp.add_table(L.out.table, false);
-            if (L.keys && cv.ok()) g_bad |= (L.out.table.status != nullptr) != tab || L.out.payload_cap != b;
+            if (L.k.keys && cv.ok()) g_bad |= (L.out.table.status != nullptr) != tab || L.out.payload_cap != b;
+            g_bad |= !flat_prefix(cv, L.k, a, n);
           }));
           CHECK(both_passes([&](Carver& cv, Spans& sp) {
             const bcw_encode_out d = carve_encode_out(cv, n, a, b);
@@ -211,6 +277,7 @@ int main() {
       CHECK(b.reserve(101, nullptr) && g_log == "SMSFM" && b.bytes() == 101);  // synchronise, free, allocate
       g_fail_next = true;
       CHECK(!b.reserve(200, nullptr) && g_log == "SMSFMSF" && !b && b.get() == nullptr && b.bytes() == 0);
+      CHECK(g_err == hipSuccess);  // the failed call's error does not wait for a later check of a launch
       CHECK(b.reserve(1, nullptr) && g_log == "SMSFMSFSM" && g_live == 1);
       DevBuf<uint32_t> c(std::move(b));
       CHECK(!b && b.bytes() == 0 && c && c.bytes() == 1 && g_live == 1);
@@ -229,6 +296,56 @@ int main() {
       CHECK(carve_alloc(mem, [&](Carver& cv) { ft = carve_frags(cv, 3); }) == BCW_E_NOMEM && !mem);
     }
     CHECK(g_live == 0);  // every allocation freed once
+  }
+  {  // adopt: the larger buffer of ix_grow / ix_compact / the walset's growth
+    {
+      DevBuf<uint32_t> held, other;
+      CHECK(held.alloc(8) && other.alloc(8) && g_live == 2);
+      const uint32_t *h0 = held.get(), *o0 = other.get();
+      g_log.clear();
+      {
+        DevBuf<uint32_t> nw;
+        CHECK(nw.alloc(16));
+        const uint32_t* pn = nw.get();
+        held.adopt(std::move(nw), nullptr);
+        CHECK(!nw && held.get() == pn && held.bytes() == 16 && pn != h0);
+      }
+      CHECK(g_log == "MSF" && g_live == 2);  // the new allocation, the synchronise, the free of the old one: once
+      DevBuf<uint32_t> empty, nw;
+      CHECK(nw.alloc(4));
+      g_log.clear();
+      empty.adopt(std::move(nw), nullptr);
+      CHECK(g_log == "S" && empty && !nw && g_live == 3);  // nothing was held: nothing freed
+      const uint32_t* h1 = held.get();
+      g_log.clear();
+      {  // a pair whose second allocation fails: the caller returns before any adopt
+        DevBuf<uint32_t> na, nb;
+        CHECK(na.alloc(32) && g_live == 4);
+        g_fail_next = true;
+        CHECK(!nb.alloc(32) && !nb && g_err == hipSuccess);
+      }
+      CHECK(g_log == "MF" && g_live == 3 && held.get() == h1 && held.bytes() == 16 && other.get() == o0);
+    }
+    CHECK(g_live == 0);
+  }
+  {  // carve_reserve
+    {
+      DevBuf<> st;
+      FlatKeys k{};
+      g_log.clear();
+      CHECK(carve_reserve(st, nullptr, [&](Carver& cv) { k = carve_flat_keys(cv, 17, 2); }) == BCW_OK);
+      CHECK(g_log == "SM" && st.bytes() == 32 + 24 && k.keys == st.get() && k.key_off);
+      void* p = st.get();
+      CHECK(carve_reserve(st, nullptr, [&](Carver& cv) { k = carve_flat_keys(cv, 1, 1); }) == BCW_OK);
+      CHECK(g_log == "SM" && st.get() == p && st.bytes() == 56 && k.keys == p);  // large enough: kept, no call
+      int pass = 0;  // 9 bytes fit the buffer, not the 8 that were measured
+      CHECK(carve_reserve(st, nullptr, [&](Carver& cv) { cv.take<uint8_t>(pass++ ? 9 : 8); }) == BCW_E_INVAL);
+      CHECK(g_log == "SM" && st.get() == p);
+      g_fail_next = true;
+      CHECK(carve_reserve(st, nullptr, [&](Carver& cv) { k = carve_flat_keys(cv, 64, 2); }) == BCW_E_NOMEM);
+      CHECK(g_log == "SMSF" && !st && st.bytes() == 0 && g_err == hipSuccess);
+    }
+    CHECK(g_live == 0);
   }
   std::printf("devmem_check ok: %llu layouts\n", layouts);
   return 0;
