@@ -1,9 +1,15 @@
 // bcw_parse.h -- the record payload parsers shared by the decode (bcw_decode.hip) and the point reads
 // (bcw_read.hip): Go encoding/binary.Uvarint with DecodeUvarint's error mapping (utils.go:51-57),
 // RecordFromBytes (record.go:140-239) and HintRecord.Decode (hint.go:50-84), over any byte accessor
-// `rd(pos)` of the payload.
+// `rd(pos)` of the payload. Plain inline functions: the kernels compile them, and so does the stand-alone host check
+// (tools/parse_check.cpp), as bcw_frame.h's are. No device calls here.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define BCW_PARSE_FN __device__ __forceinline__
+#else
+#define BCW_PARSE_FN inline
+#endif
 
 #include <cstdint>
 
@@ -13,7 +19,7 @@ namespace bcw {
 
 // Go encoding/binary.Uvarint over a byte accessor; DecodeUvarint maps errors to (0,0).
 template <typename RD>
-__device__ __forceinline__ uint64_t uvarint(RD& rd, uint64_t pos, uint64_t len, uint32_t& used) {
+BCW_PARSE_FN uint64_t uvarint(RD& rd, uint64_t pos, uint64_t len, uint32_t& used) {
   uint64_t x = 0;
   uint32_t s = 0;
   // rolled: each call site inlines the reader (its fragment-walk fallback included), so an unrolled loop
@@ -35,10 +41,9 @@ __device__ __forceinline__ uint64_t uvarint(RD& rd, uint64_t pos, uint64_t len, 
 }
 
 template <typename RD>
-__device__ __forceinline__ void parse_record(const bcw_decode_params& p, RD& rd, uint64_t len, uint8_t& status,
-                                             uint8_t& hdr, uint8_t& flags, uint8_t& etag_off, uint64_t& key_len,
-                                             uint64_t& val_len, uint64_t& meta_len, uint64_t& expire, uint64_t& aux0,
-                                             uint64_t& aux1) {
+BCW_PARSE_FN void parse_record(const bcw_decode_params& p, RD& rd, uint64_t len, uint8_t& status, uint8_t& hdr,
+                               uint8_t& flags, uint8_t& etag_off, uint64_t& key_len, uint64_t& val_len,
+                               uint64_t& meta_len, uint64_t& expire, uint64_t& aux0, uint64_t& aux1) {
   uint32_t used;
   status = BCW_ST_OK;
   hdr = flags = etag_off = 0;

@@ -17,6 +17,7 @@ from bitcaskdb_amd import wal as W
 pytestmark = pytest.mark.gpu
 BASE = cases.BASE
 REC_FIELDS = ("expire", "key_len", "val_len", "meta_len", "hdr_size", "flags", "etag_off", "status")
+LEN32 = ("key_len", "val_len", "meta_len")  # u32 columns: a rejected row's length of 2^32 and more shows its low half
 
 
 def check(ctx, data, offs, sizes, verify=True, ns=20, etag=20):
@@ -28,7 +29,8 @@ def check(ctx, data, offs, sizes, verify=True, ns=20, etag=20):
             assert pays[i] == opay, i
             r = O.record_parse(opay, BASE, ns, etag)
             for f in REC_FIELDS:
-                assert int(tab[f][i]) == int(r[f]), (i, f, int(tab[f][i]), int(r[f]))
+                want = int(r[f]) & 0xFFFFFFFF if f in LEN32 else int(r[f])
+                assert int(tab[f][i]) == want, (i, f, int(tab[f][i]), want)
             assert int(tab["foff"][i]) == o + 7 and int(tab["size"][i]) == z
     return st
 
