@@ -5,7 +5,8 @@ is the Python host mirror of the reference interface (wal.py: the WAL iterators,
 hint rebuild; index.py: the device-resident index, its rebuild from hint / data WALs, the device
 compaction filter and the batched Get by key against resident WALs; write.py: the batched Write into the
 active WAL's resident image; usage.py: live and freed bytes per WAL file for the compaction picker; scrub.py: every
-index entry verified against the resident WALs) and its ctypes binding (_lib.py).
+index entry verified against the resident WALs; scan.py: the index listed and folded by key prefix) and its ctypes
+binding (_lib.py).
 """
 from . import _lib
 from .wal import (Context, Decoded, ErrCorruptedHintRecord, ErrInvalidData, ErrShortFile, ErrWalMismatchBlockSize,
@@ -18,6 +19,7 @@ from .index import (ErrKeyNotFound, ErrKeySoftDeleted, GetBatch, Index, WalSet, 
 from .write import ActiveWal, WriteBatch
 from .usage import FidUsage, FidUsageMap, PickerWalInfo, default_compaction_picker, drop_fids, wal_garbage
 from .scrub import BadEntry, ScrubReport, verify_index
+from .scan import ScanGroup, ScanReport, fold_index, scan_index
 
 __all__ = ["Context", "Decoded", "ErrCorruptedHintRecord", "ErrInvalidData", "ErrShortFile",
            "ErrWalMismatchBlockSize", "ErrWalMismatchCRC", "ErrWalMismatchMagic", "ErrWalUnknownRecordType",
@@ -26,4 +28,5 @@ __all__ = ["Context", "Decoded", "ErrCorruptedHintRecord", "ErrInvalidData", "Er
            "new_hint_by_wal", "ErrKeyNotFound", "ErrKeySoftDeleted", "Index", "compact_one_wal_filtered",
            "merged_key", "murmur3_sum64", "recover_from_wals", "Stage", "WalSet", "GetBatch", "ActiveWal",
            "WriteBatch", "FidUsage", "PickerWalInfo", "default_compaction_picker", "wal_garbage",
-           "FidUsageMap", "drop_fids", "BadEntry", "ScrubReport", "verify_index"]
+           "FidUsageMap", "drop_fids", "BadEntry", "ScrubReport", "verify_index", "ScanGroup", "ScanReport", "scan_index",
+           "fold_index"]

@@ -143,6 +143,26 @@ class VerifyResult(C.Structure):
                 ("per_fid", UsageResult), ("fits", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class ScanParams(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("n_prefix", C.c_uint32), ("prefixes", C.c_void_p), ("prefix_off", C.c_void_p)]
+
+
+class ScanGroup(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("bytes", C.c_uint64), ("key_bytes", C.c_uint64),
+                ("soft_deleted", C.c_uint64)]
+
+
+class ScanOut(C.Structure):
+    _fields_ = [("keys", C.c_void_p), ("keys_cap", C.c_uint64), ("key_off", C.c_void_p), ("fid", C.c_void_p),
+                ("off", C.c_void_p), ("size", C.c_void_p), ("prefix_id", C.c_void_p), ("entries_cap", C.c_uint64),
+                ("groups", C.c_void_p)]
+
+
+class ScanResult(C.Structure):
+    _fields_ = [("n_listed", C.c_uint64), ("key_bytes", C.c_uint64), ("bytes", C.c_uint64),
+                ("n_soft_deleted", C.c_uint64), ("n_live", C.c_uint64), ("fits", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class IndexResult(C.Structure):
     _fields_ = [("n_in", C.c_uint64), ("n_done", C.c_uint64), ("err_class", C.c_int32), ("_pad", C.c_int32)]
 
@@ -210,6 +230,7 @@ RECOVER_NOT_RUN, RECOVER_HINT, RECOVER_HINT_WAL, RECOVER_WAL = 0, 1, 2, 3
 RD_OK, RD_BEYOND, RD_CORRUPTED, RD_CRC, RD_SIZE, RD_TYPE, RD_INCOMPLETE, RD_PANIC = range(8)
 GET_OK, GET_NOT_FOUND, GET_SOFT_DELETED, GET_NO_WAL, GET_READ, GET_RECORD = range(6)
 VFY_OK, VFY_NO_WAL, VFY_READ, VFY_RECORD, VFY_KEY = range(5)  # bcw_index_verify*: the class of a checked entry
+SCAN_SOFT_DELETED = 1  # bcw_scan_params.flags: also list matching entries with off == 0
 
 
 def _load():
@@ -302,6 +323,8 @@ def _load():
                                           C.POINTER(UsageResult)]),
         "bcw_index_verify_async": (C.c_int, [vp, vp, C.POINTER(GetParams), C.POINTER(VerifyOut), vp]),
         "bcw_index_verify": (C.c_int, [vp, vp, C.POINTER(GetParams), C.POINTER(VerifyOut), C.POINTER(VerifyResult)]),
+        "bcw_index_scan_async": (C.c_int, [vp, C.POINTER(ScanParams), C.POINTER(ScanOut), vp]),
+        "bcw_index_scan": (C.c_int, [vp, C.POINTER(ScanParams), C.POINTER(ScanOut), C.POINTER(ScanResult)]),
         "bcw_record_encode": (C.c_int64, [vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp,
                                           C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
         "bcw_write_bound": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64]),

@@ -35,7 +35,7 @@ def build(force: bool = False, verbose: bool = True, sanitize: bool = False) -> 
                                                           "bcw_walset.h", "bcw_rules.h", "bcw_usage.h", "bcw_frame.h",
                                                           "bcw_crc_dev.h", "bcw_drop.h", "bcw_murmur.h", "bcw_host.h",
                                                           "bcw_devmem.h", "bcw_crc_consts.h", "bcw_crc_tables.h",
-                                                          "bcw_verify.h")] + \
+                                                          "bcw_verify.h", "bcw_scan.h")] + \
         [os.path.join(ROOT, "include", "bcw.h")]
     if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps):
         return out

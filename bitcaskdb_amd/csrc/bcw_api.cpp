@@ -304,7 +304,7 @@ static const char* kKernelNames[K_NUM] = {"k_chase", "k_crc", "(retired)", "k_en
                                           "k_get_scan", "k_get_read", "k_put_prep", "k_put_layout", "k_put_frags",
                                           "k_put_write", "k_put_index", "k_ix_usage", "k_usage_rows",
                                           "k_usage_final", "k_ix_live_bytes", "k_ix_drop", "k_ix_vfy_select",
-                                          "k_vfy_read"};
+                                          "k_vfy_read", "k_ix_scan_select", "k_ix_scan_offsets", "k_ix_scan_emit"};
 
 int bcw_ctx_reserve_fragments(bcw_ctx* c, uint64_t n) {
   if (!c || n >= 0xfffffff0ull) return BCW_E_INVAL;

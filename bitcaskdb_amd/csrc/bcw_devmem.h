@@ -1,7 +1,7 @@
 // bcw_devmem.h -- host only: who owns a device allocation (DevBuf), how one allocation is cut into arrays (Carver), and
 // what is cut with it: the record table's column list, written once, and every layout of the library: the synchronous
 // entry points' (fragments, read, get, put, encode outputs) and the index's (flat keys, apply, get, export, usage
-// rows, scrub queue).
+// rows, scrub queue, scan scratch).
 // The two types each hold one condition: an allocation is freed exactly once; the bytes allocated are the end of the
 // very walk that hands out the pointers. tools/devmem_check.cpp compiles this against stand-ins (BCW_DEVMEM_NO_HIP).
 #pragma once
@@ -355,6 +355,20 @@ struct VfyQueueLayout {
 };
 inline VfyQueueLayout carve_vfy_queue(Carver& cv, uint64_t words, uint64_t slots, uint64_t item_bytes) {
   return {cv.take<unsigned long long>(words, 16), cv.take<uint8_t>(slots * item_bytes, 16)};
+}
+
+// the scan by prefix: the packed prefix table (table_bytes: rules::PrefixTable), `words` accumulator words (the group
+// rows and the live count, scan::kAccWords), per tile of 256 slots its listed entries and their key bytes (then their
+// exclusive prefixes), and a verdict byte per slot
+struct IxScanLayout {
+  void* table;
+  unsigned long long* acc;
+  uint64_t *tile_n, *tile_b;
+  uint8_t* verdict;
+};
+inline IxScanLayout carve_ix_scan(Carver& cv, uint64_t table_bytes, uint64_t words, uint64_t tiles, uint64_t slots) {
+  return {cv.take<uint8_t>(table_bytes, 16), cv.take<unsigned long long>(words, 16), cv.take<uint64_t>(tiles, 16),
+          cv.take<uint64_t>(tiles), cv.take_bytes16(slots)};  // a braced list: in this order
 }
 
 }  // namespace bcw

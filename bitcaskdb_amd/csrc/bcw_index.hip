@@ -30,6 +30,8 @@
 //               takes none)
 //   k_ix_write  the winning op writes the value / presence
 // Lookups (Get, the compaction filter) are one launch: hash, probe, compare.
+// The passes over the whole slot table (usage, drop, the scrub's select, the scan by key prefix) share one coalesced,
+// LDS-staged round of 256 slots (usage_round).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,6 +47,7 @@
 #include "bcw_murmur.h"
 #include "bcw_read_body.h"
 #include "bcw_rules.h"
+#include "bcw_scan.h"
 #include "bcw_usage.h"
 #include "bcw_verify.h"
 
@@ -1217,6 +1220,268 @@ __global__ __launch_bounds__(usage::kThreads) void k_ix_vfy_select(const Slot* _
   }
 }
 
+// ---- scan by key prefix (bcw_index_scan*, bcw_scan.h): list and fold a namespace ------------------------------------
+// Three stream-ordered launches, so every hand-off between workgroups is a kernel boundary:
+//   k_ix_scan_select   the usage rounds with the slot's kref: a live lane reads its arena entry's length and the key
+//                      chunks a prefix can reach, scan::decide names its group; out go a verdict byte per slot, each
+//                      256-slot tile's listed entries and key bytes, and the group rows
+//   k_ix_scan_offsets  one workgroup: the exclusive prefix sums of the two tile columns, in place, 1024 tiles a round
+//                      with a carry (any tile count), then the result, `fits` and the caller's group rows
+//   k_ix_scan_emit     a workgroup per tile: the verdict bytes, coalesced; slots and arena only for listed lanes; the
+//                      rank inside the tile by ballot and popcount over its waves; offsets, columns, keys
+// An entry's place in the output is the number of listed slots before its own, so the layout is in slot order and the
+// same bytes come out whatever the scheduling. Nothing here writes the index.
+// workgroups per CU the select and emit grids are capped at (both stride over the tiles beyond that): the select pass
+// holds 22.6 KiB of LDS and 16 KiB of loads in flight per workgroup, the emit pass next to nothing
+constexpr uint32_t kScanSelectPerCu = 4, kScanEmitPerCu = 8;
+
+struct ScanArgs {
+  const rules::PrefixTable* table;  // device; read only when n_prefix > 0
+  uint32_t n_prefix, longest, flags;
+  uint8_t* verdict;                 // [slots] 0: not listed, 1 + group
+  uint64_t *tile_n, *tile_b;        // [tiles] listed entries, their key bytes
+  unsigned long long* acc;          // [scan::kAccWords] the group rows and the live count, zeroed by the call
+};
+
+// the entry a slot's kref names lies inside the arena (always, for a consistent index: checked, not assumed, before
+// it is read, as k_ix_compact does); *len: the key's length
+__device__ __forceinline__ bool scan_entry(const uint8_t* __restrict__ arena, uint64_t arena_cap, uint64_t kref,
+                                           uint32_t* len) {
+  const uint64_t a = kref - 1;
+  if (kref == 0 || (kref & kProv) || (a & 15u) || a + 16 > arena_cap) return false;
+  *len = entry_len(arena, kref);
+  return a + entry_bytes(*len) <= arena_cap;
+}
+
+// The group rows go through a per-workgroup accumulator in LDS: the lanes of a wave that share a group (all of them,
+// when one namespace is scanned) are summed by ballot and butterfly and added by one lane, one round of the loop per
+// distinct group in the wave; the workgroup adds each non-zero word to its global word once, at the end (k_ix_drop's
+// note on measured contention). The tile columns are plain stores: every tile belongs to one round of one workgroup.
+// A wave with no live lane loads nothing and matches nothing; it still stores its 64 verdict bytes, which nothing
+// else zeroes.
+__global__ __launch_bounds__(usage::kThreads) void k_ix_scan_select(const Slot* __restrict__ slots, uint64_t cap,
+                                                                    const uint8_t* __restrict__ arena,
+                                                                    uint64_t arena_cap, ScanArgs A) {
+  static_assert(kUsageSlots == scan::kTileSlots, "a tile is one usage round");
+  __shared__ __align__(16) rules::PrefixTable pt;
+  __shared__ uint4 stage[kUsageSlots * 4];
+  __shared__ unsigned long long s_acc[scan::kAccWords];
+  __shared__ uint64_t s_tile[usage::kThreads / 64][2];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  if (A.n_prefix) {
+    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(A.table->w);
+    uint4* dst = reinterpret_cast<uint4*>(pt.w);
+    for (uint32_t q = tid; q < A.n_prefix * (rules::kPrefixWords / 4); q += usage::kThreads) dst[q] = src[q];
+    if (tid < A.n_prefix) pt.len[tid] = A.table->len[tid];
+  }
+  for (uint32_t q = tid; q < scan::kAccWords; q += usage::kThreads) s_acc[q] = 0;
+  __syncthreads();
+  uint64_t n_live = 0;
+  for (uint64_t base = (uint64_t)blockIdx.x * kUsageSlots; base < cap; base += (uint64_t)gridDim.x * kUsageSlots) {
+    const UsageLane r = usage_round<true>(slots, cap, base, stage);
+    n_live += r.live ? 1 : 0;
+    uint32_t verdict = 0;
+    uint64_t kb = 0;
+    if (__ballot(r.live) != 0) {  // wave-uniform
+      scan::Hit h{};
+      uint32_t klen = 0;
+      if (r.live && scan_entry(arena, arena_cap, r.kref, &klen)) {
+        uint32_t kw[4 * rules::kKeyChunks] = {};
+        if (A.n_prefix) {
+          const uint32_t n = rules::key_chunks(klen, A.longest);
+          const uint4* __restrict__ q = reinterpret_cast<const uint4*>(arena + (r.kref - 1) + 16);
+#pragma unroll
+          for (uint32_t c = 0; c < rules::kKeyChunks; ++c) {
+            if (c >= n) break;
+            const uint4 x = q[c];
+            kw[4 * c] = x.x;
+            kw[4 * c + 1] = x.y;
+            kw[4 * c + 2] = x.z;
+            kw[4 * c + 3] = x.w;
+          }
+        }
+        h = scan::decide(true, r.off, r.size, kw, klen, pt.w, pt.len, A.n_prefix, A.flags);
+      }
+      for (uint64_t m = __ballot(h.match); m != 0;) {  // one round per distinct group in the wave
+        const int lead = __ffsll((unsigned long long)m) - 1;
+        const uint32_t g = __shfl(h.group, lead, 64);
+        const bool mine = h.match && h.group == g;
+        const uint64_t cnt = (uint64_t)__popcll(__ballot(mine && !h.soft));
+        const uint64_t soft = (uint64_t)__popcll(__ballot(mine && h.soft));
+        const uint64_t by = wave_sum(mine ? h.bytes : 0), kby = wave_sum(mine ? h.key_bytes : 0);
+        if ((int)lane == lead) {
+          unsigned long long* row = &s_acc[g * scan::G_WORDS];
+          if (cnt) atomicAdd(&row[scan::G_COUNT], (unsigned long long)cnt);
+          if (by) atomicAdd(&row[scan::G_BYTES], (unsigned long long)by);
+          if (kby) atomicAdd(&row[scan::G_KEY_BYTES], (unsigned long long)kby);
+          if (soft) atomicAdd(&row[scan::G_SOFT], (unsigned long long)soft);
+        }
+        m &= ~__ballot(mine);
+      }
+      verdict = scan::verdict_of(h);
+      kb = verdict ? klen : 0;
+    }
+    if (base + tid < cap) A.verdict[base + tid] = (uint8_t)verdict;
+    const uint64_t lm = __ballot(verdict != 0);
+    if (lm) kb = wave_sum(kb);  // wave-uniform
+    if (lane == 0) {
+      s_tile[wave][0] = (uint64_t)__popcll(lm);
+      s_tile[wave][1] = kb;
+    }
+    __syncthreads();  // the next writes of s_tile come behind the two barriers of the next round
+    if (tid == 0) {
+      uint64_t n = 0, b = 0;
+      for (uint32_t w = 0; w < usage::kThreads / 64; ++w) { n += s_tile[w][0]; b += s_tile[w][1]; }
+      A.tile_n[scan::tile_of(base)] = n;
+      A.tile_b[scan::tile_of(base)] = b;
+    }
+  }
+  n_live = wave_sum(n_live);
+  if (lane == 0 && n_live) atomicAdd(&s_acc[scan::kLiveWord], (unsigned long long)n_live);
+  __syncthreads();
+  for (uint32_t q = tid; q < scan::kAccWords; q += usage::kThreads)
+    if (s_acc[q]) atomicAdd(&A.acc[q], s_acc[q]);
+}
+
+// One workgroup of 1024 threads: a thread per tile and round, the wave's inclusive scan by shuffles, the waves' totals
+// through LDS, the carry of the rounds before in every thread. Then the totals (bytes and n_soft_deleted are the sums
+// of the rows' columns), `fits`, the caller's group rows, and -- when the outputs are whole -- the last offset,
+// key_off[n_listed] = key_bytes (key_off[0] = 0 of an empty listing included); the emit pass writes the others.
+constexpr uint32_t kScanOffsetsThreads = 1024;
+__global__ __launch_bounds__(kScanOffsetsThreads) void k_ix_scan_offsets(uint64_t* __restrict__ tile_n,
+                                                                         uint64_t* __restrict__ tile_b, uint64_t tiles,
+                                                                         const unsigned long long* __restrict__ acc,
+                                                                         uint32_t rows, bcw_scan_out out,
+                                                                         bcw_scan_result* __restrict__ res) {
+  constexpr uint32_t kWaves = kScanOffsetsThreads / 64;
+  __shared__ uint64_t s_w[kWaves][2];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint64_t cn = 0, cb = 0;  // listed entries and key bytes of the rounds before
+  for (uint64_t t0 = 0; t0 < tiles; t0 += kScanOffsetsThreads) {
+    const uint64_t i = t0 + tid;
+    const uint64_t n = i < tiles ? tile_n[i] : 0, b = i < tiles ? tile_b[i] : 0;
+    uint64_t in = n, ib = b;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint64_t tn = __shfl_up(in, d, 64), tb = __shfl_up(ib, d, 64);
+      if (lane >= (uint32_t)d) { in += tn; ib += tb; }
+    }
+    if (lane == 63) { s_w[wave][0] = in; s_w[wave][1] = ib; }
+    __syncthreads();
+    uint64_t pn = cn, pb = cb;
+    for (uint32_t w = 0; w < kWaves; ++w) {
+      const uint64_t wn = s_w[w][0], wb = s_w[w][1];
+      if (w < wave) { pn += wn; pb += wb; }
+      cn += wn;
+      cb += wb;
+    }
+    if (i < tiles) {
+      tile_n[i] = pn + in - n;
+      tile_b[i] = pb + ib - b;
+    }
+    __syncthreads();  // the next round overwrites s_w
+  }
+  if (out.groups && tid < rows * scan::G_WORDS) reinterpret_cast<uint64_t*>(out.groups)[tid] = acc[tid];
+  if (tid != 0) return;
+  bcw_scan_result o{};
+  o.n_listed = cn;
+  o.key_bytes = cb;
+  for (uint32_t r = 0; r < rows; ++r) {
+    o.bytes += acc[r * scan::G_WORDS + scan::G_BYTES];
+    o.n_soft_deleted += acc[r * scan::G_WORDS + scan::G_SOFT];
+  }
+  o.n_live = acc[scan::kLiveWord];
+  o.fits = scan::fits(cn, out.entries_cap, cb, out.keys_cap) ? 1u : 0u;
+  *res = o;
+  if (o.fits && out.key_off) out.key_off[cn] = cb;
+}
+
+// len key bytes from src (an arena key: 16-byte aligned, padded to 16) to dst (any alignment), in 16-byte granules
+// aligned to the destination. Neighbouring keys share destination granules, and those keys may be written by other
+// waves or workgroups at the same time, so no granule that holds another key's bytes is read or written whole: the
+// bytes before the first granule that lies inside this key, and those behind the last one, are byte stores; every
+// 16-byte store covers only bytes of this key. A whole granule is bytes [o, o + 16) of the key, unaligned in the
+// arena by the head's length: the two-chunk funnel (shift16), each chunk loaded once. Chunk c + 1 is read only when a
+// byte of it is needed, so never past the entry.
+__device__ __forceinline__ void scan_copy_key(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src,
+                                              uint32_t len) {
+  const uint32_t lead = (16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u;
+  const uint32_t head = lead < len ? lead : len;
+  for (uint32_t q = 0; q < head; ++q) dst[q] = src[q];
+  uint32_t o = head;
+  if (len - o >= 16) {
+    const uint4* __restrict__ s = reinterpret_cast<const uint4*>(src);
+    const uint32_t sh = head;  // o % 16 of every granule
+    uint32_t c = 0;
+    uint4 v0 = s[0];
+    for (; len - o >= 16; o += 16, ++c) {
+      uint4 v = v0;
+      if (sh) {
+        const uint4 v1 = s[c + 1];  // holds key byte 16 c + 16 <= o + 15 < len
+        v = shift16(v0, v1, sh);
+        v0 = v1;
+      } else if (len - o >= 32) {
+        v0 = s[c + 1];
+      }
+      *reinterpret_cast<uint4*>(dst + o) = v;
+    }
+  }
+  for (; o < len; ++o) dst[o] = src[o];
+}
+
+// Bounds: a listed lane's entry passed scan_entry in the select pass of the same call, on the same buffers; its place
+// (pc, pb) is a prefix sum of the very counts `fits` was decided from, and is checked against the caps all the same
+// before anything is stored.
+__global__ __launch_bounds__(scan::kTileSlots) void k_ix_scan_emit(const Slot* __restrict__ slots, uint64_t cap,
+                                                                   const uint8_t* __restrict__ arena,
+                                                                   const uint8_t* __restrict__ verdict,
+                                                                   const uint64_t* __restrict__ tile_n,
+                                                                   const uint64_t* __restrict__ tile_b, uint64_t tiles,
+                                                                   bcw_scan_out out,
+                                                                   const bcw_scan_result* __restrict__ res) {
+  constexpr uint32_t kWaves = scan::kTileSlots / 64;
+  __shared__ uint64_t s_w[kWaves][2];
+  if (res->fits == 0) return;
+  const uint64_t n_listed = res->n_listed;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const uint64_t t0 = tile_n[tile], t1 = tile + 1 < tiles ? tile_n[tile + 1] : n_listed;
+    if (t1 == t0) continue;  // nothing listed in this tile (uniform over the workgroup)
+    const uint64_t i = scan::tile_base(tile) + tid;
+    const uint32_t v = i < cap ? verdict[i] : 0u;
+    const bool listed = v != 0;
+    uint64_t kref = 0, fid = 0, off = 0, size = 0;
+    uint32_t klen = 0;
+    if (listed) {
+      const Slot& S = slots[i];
+      kref = S.kref;
+      fid = S.fid;
+      off = S.off;
+      size = S.size;
+      klen = entry_len(arena, kref);
+    }
+    const uint64_t lm = __ballot(listed);
+    uint64_t ib = klen;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint64_t tb = __shfl_up(ib, d, 64);
+      if (lane >= (uint32_t)d) ib += tb;
+    }
+    if (lane == 63) { s_w[wave][0] = (uint64_t)__popcll(lm); s_w[wave][1] = ib; }
+    __syncthreads();
+    uint64_t pc = t0 + (uint64_t)__popcll(lm & ((1ull << lane) - 1ull)), pb = tile_b[tile] + ib - klen;
+    for (uint32_t w = 0; w < wave; ++w) { pc += s_w[w][0]; pb += s_w[w][1]; }
+    __syncthreads();  // the next tile overwrites s_w
+    if (!listed || pc >= out.entries_cap || pb + klen > out.keys_cap) continue;
+    out.key_off[pc] = pb;
+    if (out.fid) out.fid[pc] = fid;
+    if (out.off) out.off[pc] = off;
+    if (out.size) out.size[pc] = size;
+    if (out.prefix_id) out.prefix_id[pc] = (uint8_t)scan::verdict_group(v);
+    scan_copy_key(out.keys + pb, arena + (kref - 1) + 16, klen);
+  }
+}
+
 }  // namespace ix
 }  // namespace bcw
 
@@ -1259,6 +1524,13 @@ struct bcw_index {
   // the vfy_q_cap slots of the largest table a scrub has met (carve_vfy_queue)
   DevBuf<> vfy_q;
   uint64_t vfy_q_cap = 0;
+  // the scan's scratch (bcw_index_scan*; grow-only, allocated with the first scan), carved for the scan_cap slots of
+  // the largest table a scan has met (carve_ix_scan), and the packed prefix table in pinned host memory with the event
+  // behind its last copy to the device, as for the drop's fid list
+  DevBuf<> scan_mem;
+  uint64_t scan_cap = 0;
+  rules::PrefixTable* scan_h = nullptr;
+  hipEvent_t scan_ev = nullptr;
 };
 
 namespace {
@@ -1718,6 +1990,8 @@ int bcw_index_destroy(bcw_index* x) {
   (void)hipStreamSynchronize(x->ctx->cur);
   if (x->drop_h) (void)hipHostFree(x->drop_h);
   if (x->drop_ev) (void)hipEventDestroy(x->drop_ev);
+  if (x->scan_h) (void)hipHostFree(x->scan_h);
+  if (x->scan_ev) (void)hipEventDestroy(x->scan_ev);
   delete x;  // the device buffers go here (DevBuf), on the index's device: inside dg's scope
   return BCW_OK;
 }
@@ -2087,6 +2361,113 @@ int bcw_index_drop_fids(bcw_index* x, int mode, const uint64_t* h_fids, uint32_t
   return ix_usage_sync(x, h_rows, cap, h_res, false, [&](bcw_fid_usage* d_rows, bcw_usage_result* d_res) {
     return bcw_index_drop_fids_async(x, mode, h_fids, n_fids, d_rows, cap, d_res);
   });
+}
+
+int bcw_index_scan_async(bcw_index* x, const bcw_scan_params* p, const bcw_scan_out* d_out, bcw_scan_result* d_res) {
+  if (!x || !d_res || scan::validate(p, d_out) != BCW_OK) return BCW_E_INVAL;  // nothing has touched the stream yet
+  bcw_ctx* c = x->ctx;
+  DeviceGuard dg(c->device);
+  if (!dg.ok) return BCW_E_HIP;
+  hipStream_t st = c->cur;
+  // grow-only: a table that shrank since keeps the scratch, and the capacity, of the largest one
+  const uint64_t cap = std::max(x->cap, x->scan_cap);
+  IxScanLayout L;
+  const auto layout = [&](Carver& cv) {
+    L = carve_ix_scan(cv, sizeof(rules::PrefixTable), scan::kAccWords, scan::tiles(cap), cap);
+  };
+  int rc = carve_reserve(x->scan_mem, st, layout);
+  x->scan_cap = rc == BCW_OK ? cap : 0;
+  if (rc != BCW_OK) return rc;
+  if (!x->scan_h) {
+    if (hipHostMalloc(reinterpret_cast<void**>(&x->scan_h), sizeof(rules::PrefixTable), hipHostMallocDefault) !=
+            hipSuccess ||
+        hipEventCreateWithFlags(&x->scan_ev, hipEventDisableTiming) != hipSuccess) {
+      if (x->scan_h) (void)hipHostFree(x->scan_h);
+      (void)hipGetLastError();
+      x->scan_h = nullptr;
+      x->scan_ev = nullptr;
+      return BCW_E_NOMEM;
+    }
+  } else if (hipEventSynchronize(x->scan_ev) != hipSuccess) {  // the previous call's copy has read the pinned table
+    return BCW_E_HIP;
+  }
+  ScanArgs A{};
+  A.table = static_cast<const rules::PrefixTable*>(L.table);
+  A.n_prefix = p->n_prefix;
+  A.flags = p->flags;
+  A.verdict = L.verdict;
+  A.tile_n = L.tile_n;
+  A.tile_b = L.tile_b;
+  A.acc = L.acc;
+  if (p->n_prefix) {
+    A.longest = scan::pack(*p, x->scan_h);
+    if (hipMemcpyAsync(L.table, x->scan_h, sizeof(rules::PrefixTable), hipMemcpyHostToDevice, st) != hipSuccess)
+      return BCW_E_HIP;
+  }
+  if (hipEventRecord(x->scan_ev, st) != hipSuccess ||
+      hipMemsetAsync(L.acc, 0, scan::kAccWords * sizeof *L.acc, st) != hipSuccess)
+    return BCW_E_HIP;
+  // the buffers are taken as they are now: a batch queued before this call has already grown them
+  const uint64_t tiles = scan::tiles(x->cap);
+  const uint32_t wgs = (uint32_t)std::min<uint64_t>(tiles, 0x7fffffffull);
+  hipEvent_t ev = nullptr;
+  c->prof.begin(K_SCAN_SELECT, st, ev);
+  k_ix_scan_select<<<std::min(wgs, (uint32_t)c->num_cus * kScanSelectPerCu), usage::kThreads, 0, st>>>(
+      x->slots.get(), x->cap, x->arena.get(), x->arena.bytes(), A);
+  c->prof.end(K_SCAN_SELECT, st, ev);
+  c->prof.begin(K_SCAN_OFFSETS, st, ev);
+  k_ix_scan_offsets<<<1, kScanOffsetsThreads, 0, st>>>(L.tile_n, L.tile_b, tiles, L.acc,
+                                                        scan::group_rows(p->n_prefix), *d_out, d_res);
+  c->prof.end(K_SCAN_OFFSETS, st, ev);
+  c->prof.begin(K_SCAN_EMIT, st, ev);
+  k_ix_scan_emit<<<std::min(wgs, (uint32_t)c->num_cus * kScanEmitPerCu), scan::kTileSlots, 0, st>>>(
+      x->slots.get(), x->cap, x->arena.get(), L.verdict, L.tile_n, L.tile_b, tiles, *d_out, d_res);
+  c->prof.end(K_SCAN_EMIT, st, ev);
+  return hipGetLastError() == hipSuccess ? BCW_OK : BCW_E_HIP;
+}
+
+int bcw_index_scan(bcw_index* x, const bcw_scan_params* p, const bcw_scan_out* h_out, bcw_scan_result* h_res) {
+  if (!x || !h_res || scan::validate(p, h_out) != BCW_OK) return BCW_E_INVAL;
+  const bcw_scan_out& h = *h_out;
+  bcw_ctx* c = x->ctx;
+  DeviceGuard dg(c->device);
+  if (!dg.ok) return BCW_E_HIP;
+  hipStream_t st = c->cur;
+  const uint32_t rows = scan::group_rows(p->n_prefix);
+  DevBuf<> mem;
+  bcw_scan_out d{};
+  bcw_scan_result* d_res = nullptr;
+  if (const int rc = carve_alloc(mem, [&](Carver& cv) {
+        d_res = cv.take<bcw_scan_result>(1, 16);
+        d.groups = h.groups ? cv.take<bcw_scan_group>(rows, 16) : nullptr;
+        d.keys = h.keys ? cv.take_bytes16(h.keys_cap) : nullptr;
+        d.key_off = h.key_off ? cv.take<uint64_t>(h.entries_cap + 1) : nullptr;
+        d.fid = h.fid ? cv.take<uint64_t>(h.entries_cap) : nullptr;
+        d.off = h.off ? cv.take<uint64_t>(h.entries_cap) : nullptr;
+        d.size = h.size ? cv.take<uint64_t>(h.entries_cap) : nullptr;
+        d.prefix_id = h.prefix_id ? cv.take<uint8_t>(h.entries_cap) : nullptr;
+        cv.take<uint8_t>(kTailSlack);
+      }))
+    return rc;
+  d.keys_cap = h.keys ? h.keys_cap : 0;
+  d.entries_cap = h.entries_cap;
+  int rc = bcw_index_scan_async(x, p, &d, d_res);
+  if (rc == BCW_OK)
+    rc = copy_down(h_res, d_res, sizeof *h_res, st) && copy_down(h.groups, d.groups, rows * sizeof(bcw_scan_group), st) &&
+                 hipStreamSynchronize(st) == hipSuccess
+             ? BCW_OK
+             : BCW_E_HIP;
+  if (rc == BCW_OK && !h_res->fits) rc = BCW_E_CAPACITY;
+  if (rc == BCW_OK) {
+    const uint64_t n = h_res->n_listed;
+    const bool ok = copy_down(h.keys, d.keys, h_res->key_bytes, st) &&
+                    copy_down(h.key_off, d.key_off, 8 * (n + 1), st) && copy_down(h.fid, d.fid, 8 * n, st) &&
+                    copy_down(h.off, d.off, 8 * n, st) && copy_down(h.size, d.size, 8 * n, st) &&
+                    copy_down(h.prefix_id, d.prefix_id, n, st) && hipStreamSynchronize(st) == hipSuccess;
+    if (!ok) rc = BCW_E_HIP;
+  }
+  (void)hipStreamSynchronize(st);  // before mem goes
+  return rc;
 }
 
 // the hash of the index (bcw_murmur.h: the text the kernels compile), over a byte pointer

@@ -81,7 +81,7 @@ struct Scratch {
 enum KernelId { K_CHASE = 0, K_CRC, K_RETIRED, K_ENC_PREP, K_ENC_SCAN, K_ENC_EVENTS, K_ENC_WRITE, K_ENC_HINT_LAYOUT,
                 K_ENC_EVENTS_HINT, K_GET_LOOKUP, K_GET_SCAN, K_GET_READ, K_PUT_PREP, K_PUT_LAYOUT, K_PUT_FRAGS,
                 K_PUT_WRITE, K_PUT_INDEX, K_USAGE_INDEX, K_USAGE_ROWS, K_USAGE_FINAL, K_IX_LIVE_BYTES, K_IX_DROP,
-                K_VFY_SELECT, K_VFY_READ, K_NUM };
+                K_VFY_SELECT, K_VFY_READ, K_SCAN_SELECT, K_SCAN_OFFSETS, K_SCAN_EMIT, K_NUM };
 struct Prof {
   uint32_t mask = 0;   // bit k: time kernel id k
   uint32_t every = 1;  // time every `every`-th launch of a selected kernel

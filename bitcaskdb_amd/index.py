@@ -7,6 +7,7 @@ Names, argument meaning and error behaviour follow wenzhang-dev/bitcaskDB:
   compact_one_wal_filtered                 compactOneWal with doFilter       compaction.go:294-348
   Index.get_records / WalSet               DBImpl.Get / getWalRef            db_impl.go:567-593, 607-619
   Index.write (write.py)                   DBImpl.writeWal + writeIndex      db_impl.go:434-480
+  Index.scan / Index.fold (scan.py)        no counterpart: list_keys and fold of classical Bitcask, by key prefix
 The index lives in HBM (bcw_index); every operation goes through the C-ABI, there is no host fallback.
 """
 from __future__ import annotations
@@ -133,6 +134,31 @@ class GetBatch:
     def record_bytes(self, i: int) -> bytes:
         o = int(self.pay_off[i])
         return bytes(self.payload[o:o + int(self.size[i])])
+
+
+def _get_items(b: GetBatch, n: int, ns_size: int, etag_size: int) -> list:
+    """the n requests of a bcw_get_records* call as Index.get_records returns them: a wal.Record, or the error
+    instance the reference's Get returns for the key (not raised)"""
+    view = Decoded(result=L.DecodeResult(), table=b.table, seg=None, mode=L.MODE_RECORD, ns_size=ns_size,
+                   etag_size=etag_size)
+    out = []
+    for i in range(n):
+        g = int(b.get_status[i])
+        if g == L.GET_OK:
+            out.append(_record_of(view, i, b.record_bytes(i)))
+        elif g in (L.GET_NOT_FOUND, L.GET_NO_WAL):
+            out.append(ErrKeyNotFound())
+        elif g == L.GET_SOFT_DELETED:
+            out.append(ErrKeySoftDeleted())
+        elif g == L.GET_READ:
+            out.append(_RD_ERRORS[int(b.rd_status[i])]())
+        elif b.table["status"][i] == L.ST_INVALID:
+            out.append(ErrInvalidData())
+        elif b.table["status"][i] == L.ST_PANIC:
+            out.append(RefPanic("slice bounds out of range"))
+        else:
+            out.append(WalError("record length >= 2^32 is not supported by the device table"))
+    return out
 
 
 class Index:
@@ -383,26 +409,22 @@ class Index:
         b = self.get_batch(walset, keys, verify, ns_size, etag_size)
         if b.rc != 0:
             raise RuntimeError(f"bcw_get_records: {L.lib.bcw_strerror(b.rc).decode()}")
-        view = Decoded(result=L.DecodeResult(), table=b.table, seg=None, mode=L.MODE_RECORD, ns_size=ns_size,
-                       etag_size=etag_size)
-        out = []
-        for i in range(len(keys)):
-            g = int(b.get_status[i])
-            if g == L.GET_OK:
-                out.append(_record_of(view, i, b.record_bytes(i)))
-            elif g in (L.GET_NOT_FOUND, L.GET_NO_WAL):
-                out.append(ErrKeyNotFound())
-            elif g == L.GET_SOFT_DELETED:
-                out.append(ErrKeySoftDeleted())
-            elif g == L.GET_READ:
-                out.append(_RD_ERRORS[int(b.rd_status[i])]())
-            elif b.table["status"][i] == L.ST_INVALID:
-                out.append(ErrInvalidData())
-            elif b.table["status"][i] == L.ST_PANIC:
-                out.append(RefPanic("slice bounds out of range"))
-            else:
-                out.append(WalError("record length >= 2^32 is not supported by the device table"))
-        return out
+        return _get_items(b, len(keys), ns_size, etag_size)
+
+    # ---- scan by key prefix: list and fold a namespace (no counterpart in the reference) ----
+    def scan(self, prefixes=None, soft_deleted: bool = False):
+        """the live entries whose merged key starts with one of `prefixes` (None: every entry) and one row of counts
+        per prefix: a scan.ScanReport with entries {merged key: (fid, off, size)} and groups (bcw_index_scan: one
+        read-only pass over the slot table); see scan.scan_index"""
+        from .scan import scan_index
+        return scan_index(self, prefixes, soft_deleted)
+
+    def fold(self, walset: "WalSet", prefixes, verify: bool = False, ns_size: int = 20, etag_size: int = 20,
+             soft_deleted: bool = False):
+        """every record under `prefixes`: (keys, items), items as get_records returns them; the keys go from the scan
+        to the Get without leaving HBM (bcw_index_scan_async + bcw_get_records_async); see scan.fold_index"""
+        from .scan import fold_index
+        return fold_index(self, walset, prefixes, verify, ns_size, etag_size, soft_deleted)
 
     # ---- batched Write (DBImpl.Write's writeWal + writeIndex, db_impl.go:434-480) ----
     def write(self, active, batch, walset=None, ns_size: int = 20, etag_size: int = 20,

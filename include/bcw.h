@@ -945,6 +945,69 @@ int bcw_index_verify_async(bcw_index* ix, bcw_walset* ws, const bcw_get_params* 
 int bcw_index_verify(bcw_index* ix, bcw_walset* ws, const bcw_get_params* p, const bcw_verify_out* h_out,
                      bcw_verify_result* h_res);
 
+/* ---- scan by key prefix: list and fold a namespace in HBM -----------------------------------------------------
+ * Every call above that reads a value needs its key. This one answers what a user of a namespaced store asks first --
+ * which keys does a namespace hold, how many, how many bytes -- and hands the keys on to bcw_get_records_async without
+ * their leaving HBM (classical Bitcask's list_keys and fold). The reference has no counterpart: its hash map gives it
+ * no better way than a full walk, and a full walk of the slot table is what the device does cheaply. One read-only
+ * pass over the table, nothing is modified.
+ * Matching. A slot that is not live is ignored. A live entry matches when n_prefix == 0, or when its merged key
+ * ns || key starts with one of the prefixes; its group is the first prefix that matches, in the order given
+ * (BCW_RULE_PREFIX's rule: a prefix longer than the key never matches, a duplicate of an earlier prefix collects
+ * nothing). With n_prefix == 0 there is one group, row 0.
+ * Listing and counting. A matching entry with off != 0 is listed -- values 0 < off < 40 included, Get finds those
+ * too -- and adds 1 to its group's count, its size to bytes and its key length to key_bytes. A matching entry with
+ * off == 0 is a SoftDelete (index.go:125-142): it adds 1 to its group's soft_deleted and to n_soft_deleted, and is
+ * listed only with BCW_SCAN_SOFT_DELETED, then with fid, off and size as stored (zeros). Group rows and totals are
+ * wrapping uint64 sums and exact whatever the caps.
+ * Layout. Entry i's key is keys[key_off[i], key_off[i+1]), key_off[0] == 0, key_off[n_listed] == key_bytes: the
+ * (d_keys, d_key_off) pair bcw_get_records_async takes. Entries come out in ascending slot order, so the layout does
+ * not depend on scheduling and two scans of an unchanged index write identical bytes; with respect to keys that is no
+ * particular order, as for bcw_index_export.
+ * Caps. fits = n_listed <= entries_cap && key_bytes <= keys_cap. With fits == 0 no key byte, no offset and no column
+ * entry is written; groups and the result still are. NULL arrays with caps 0 give the totals only. */
+#define BCW_SCAN_SOFT_DELETED 1u   /* also list matching entries with off == 0 */
+
+typedef struct bcw_scan_params {
+  uint32_t flags;             /* BCW_SCAN_* */
+  uint32_t n_prefix;          /* 0: every live entry (one group, row 0); <= BCW_RULE_MAX_PREFIXES */
+  const uint8_t* prefixes;    /* host, as in bcw_compact_rules: prefix i = prefixes[prefix_off[i], prefix_off[i+1]) */
+  const uint32_t* prefix_off; /* host, n_prefix + 1 entries; each prefix 1..BCW_RULE_MAX_PREFIX_LEN bytes */
+} bcw_scan_params;
+
+typedef struct bcw_scan_group { uint64_t count, bytes, key_bytes, soft_deleted; } bcw_scan_group;
+
+typedef struct bcw_scan_out {
+  uint8_t* keys;  uint64_t keys_cap;     /* merged keys, packed with no padding */
+  uint64_t* key_off;                     /* entries_cap + 1 entries */
+  uint64_t* fid; uint64_t* off; uint64_t* size;  /* each may be NULL: column not wanted */
+  uint8_t* prefix_id;                    /* may be NULL; the group of the entry */
+  uint64_t entries_cap;
+  bcw_scan_group* groups;                /* max(n_prefix, 1) rows; may be NULL */
+} bcw_scan_out;
+
+typedef struct bcw_scan_result {
+  uint64_t n_listed, key_bytes;          /* what the outputs must hold; exact whatever the caps */
+  uint64_t bytes;                        /* sum of size over the listed file-backed entries (wrapping) */
+  uint64_t n_soft_deleted;               /* matching entries with off == 0 (listed only with the flag) */
+  uint64_t n_live;                       /* live entries the pass saw (== bcw_index_info.live) */
+  uint32_t fits, _pad;
+} bcw_scan_result;                       /* 48 bytes */
+
+/* Async, device-resident: the arrays of *d_out and d_res are device pointers; the two structs and the prefix arrays
+ * are host memory, copied before the call returns. Runs on the index's context stream and does not synchronise. The
+ * index is not modified; its buffers are taken at launch, as for bcw_get_records_async, so a scan queued after a batch
+ * sees the batch. One caller at a time uses the index. The scratch between the passes (a verdict byte per slot, two
+ * words per 256 slots, the group rows) is a grow-only buffer of the index, sized from its slot capacity as the
+ * scrub's queue is; it is not the context's accounting scratch.
+ * BCW_E_INVAL, with nothing launched: an unknown flag; n_prefix > BCW_RULE_MAX_PREFIXES; an empty prefix or one longer
+ * than BCW_RULE_MAX_PREFIX_LEN; offsets that descend; n_prefix > 0 with a NULL array; entries_cap > 0 with keys or
+ * key_off NULL. */
+int bcw_index_scan_async(bcw_index* ix, const bcw_scan_params* p, const bcw_scan_out* d_out, bcw_scan_result* d_res);
+/* Synchronous, host out. Returns BCW_E_CAPACITY with the result and the groups filled (no key byte, offset or column
+ * entry copied) when fits == 0, as bcw_index_verify does: retry with entries_cap = n_listed, keys_cap = key_bytes. */
+int bcw_index_scan(bcw_index* ix, const bcw_scan_params* p, const bcw_scan_out* h_out, bcw_scan_result* h_res);
+
 /* ---- host I/O staging: WAL files <-> HBM through pinned slices ---------------------------------------
  * The reference reads a segment with PreadFull per 32 KiB block (utils.go:32-48, wal_iterator.go:55)
  * and writes the rewritten WAL through a buffer flushed every >= 1 MiB (WalRewriter
